@@ -15,6 +15,11 @@ Weak scaling: each rank trains on its own batch of `--batch` activations
 Timing contract: W untimed warmup steps; barrier + torch.cuda.synchronize on
 both sides of exactly K timed steps; elapsed is MAX over ranks; rank 0 prints
 ONE JSON line.
+
+A plain run does only that.  --dump-outputs DIR additionally stores what the
+last timed step returned on rank 0 (seeded inputs: identical from run to run
+with the same arguments); --full is where any secondary measurement belongs
+(none exist yet: it is accepted and currently a no-op).
 """
 
 from __future__ import annotations
@@ -55,7 +60,67 @@ def parse_args():
     p.add_argument("--dtype", choices=["fp32"], default="fp32",
                    help="compute dtype; fp32 matches the reference (fp32 params, BASELINE.md)")
     p.add_argument("--profile-tag", default="", help="extra tag echoed in the JSON config")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned "
+                        "(loss terms and aux arrays) as DIR/<name>.npy, <= 64 MB in all; "
+                        "with --gpus N only rank 0's outputs are written; integer and bool "
+                        "arrays are stored as float32")
+    p.add_argument("--full", action="store_true",
+                   help="currently a no-op: the place for secondary measurements, of which "
+                        "this file has none yet; a plain run does only setup, warmup, the "
+                        "timed steps and the result line")
     return p.parse_args()
+
+
+DUMP_BUDGET_BYTES = 60 << 20  # array bytes; .npy headers stay well inside 64 MB
+
+
+def _named_tensors(prefix, obj, out):
+    """Flatten the (nested dict/list of) tensors a step returns into
+    {name: tensor}, names joined with '_' in sorted-key order."""
+    if torch.is_tensor(obj):
+        out[prefix] = obj
+    elif isinstance(obj, dict):
+        for k in sorted(obj, key=str):
+            _named_tensors(f"{prefix}_{k}", obj[k], out)
+    elif isinstance(obj, (list, tuple)):
+        for i, v in enumerate(obj):
+            _named_tensors(f"{prefix}_{i}", v, out)
+    return out
+
+
+def dump_outputs(out_dir, losses, aux):
+    """Write the last timed step's return values (the calling rank's; main()
+    calls this on rank 0 only) as <name>.npy: float64 tensors as float64,
+    every other dtype, integer and bool included, as float32.  An array
+    larger than its share of the 64 MB budget is stored as a fixed sample:
+    `cap` evenly spaced flat elements, index k*numel//cap, all distinct, so
+    two builds run with the same arguments store the same elements."""
+    os.makedirs(out_dir, exist_ok=True)
+    named = _named_tensors("losses", losses, {})
+    _named_tensors("aux", aux, named)
+    if not named:
+        return
+    # smallest first: arrays under an equal share are stored whole and leave
+    # their unused share to the larger ones
+    order = sorted(named, key=lambda k: named[k].numel())
+    total = 0
+    for i, name in enumerate(order):
+        t = named[name].detach()
+        flat = t.reshape(-1)
+        itemsize = 8 if flat.dtype == torch.float64 else 4
+        cap = (DUMP_BUDGET_BYTES - total) // (len(order) - i) // itemsize
+        if flat.numel() > cap:
+            idx = torch.arange(cap, device=flat.device) * flat.numel() // cap
+            flat = flat[idx]
+            arr_shape = (cap,)
+        else:
+            arr_shape = tuple(t.shape)
+        dt = torch.float64 if flat.dtype == torch.float64 else torch.float32
+        arr = flat.to(dt).cpu().numpy().reshape(arr_shape)
+        total += arr.nbytes
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+    assert total <= DUMP_BUDGET_BYTES, total
 
 
 def main():
@@ -166,6 +231,9 @@ def main():
 
     ms_per_step = elapsed / args.steps * 1000.0
     acts_per_sec = world_size * B * args.steps / elapsed
+
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, losses, aux)
 
     if rank == 0:
         result = {

@@ -255,7 +255,8 @@ class HipSAEStep:
         dict_w = enc if self.tied else p["decoder"]
 
         self.loss_parts.zero_()
-        self.g_bias.zero_()
+        if self.reverse or self.kc["staging"] == "pre":
+            self.g_bias.zero_()  # else k_gc overwrites it (accumulate=False)
         self._fired_step = self.fired  # accumulated across steps for resampling
 
         kc = self.kc
@@ -289,7 +290,7 @@ class HipSAEStep:
                         dict_sizes=self.dict_sizes)
             ext.dec_fwd(self.c, dict_w, self.inv_norms, x, self.r, self.loss_parts, bk_dec, prio, bn)
             ext.gc(self.r, dict_w, self.inv_norms, self.c, self.l1_alpha, self.gpre, self.g_bias, bk, prio,
-                   gc_mode=1 if self.reverse else 0, bn=bn_enc)
+                   gc_mode=1 if self.reverse else 0, bn=bn_enc, accumulate=False)
 
         if on_grads is not None:
             on_grads([self.g_bias])  # final after k_gc

@@ -30,7 +30,9 @@
 //   k_enc_fwd_t  : c = relu(x @ Wenc^T + b)    (+ L1 partial, fired counts)
 //   k_enc_fwd2_t : same with pre-transposed operands (all-direct staging)
 //   k_dec_fwd_t  : r = c @ Wdec_hat - x        (+ MSE partial)
-//   k_gc_t/k_gc2_t: gpre = (c>0) .* (gs * r @ Wdec_hat^T + l1/B) (+ bias-grad)
+//   k_gc_t/k_gc2_t: gpre = (c>0) .* (gs * r @ Wdec_hat^T + l1/B) (+ bias-grad;
+//                  k_gc_t stores per-32-row column sums, k_colsum_groups adds
+//                  them in a fixed order: reproducible; k_gc2_t uses atomics)
 //   k_grad_w_t   : gw = beta*gw + alpha * P^T @ Q   (K = batch contraction)
 //   k_row_norms, k_project_adam (gradient of w/max(||w||,eps)), k_bias_adam,
 //   k_transpose_scale, k_colsum (HBM-rate column sums / L1 reductions),
@@ -588,7 +590,7 @@ void k_gc_t(const float* __restrict__ r,        // [M, B, d]
             const float* __restrict__ c,        // [M, B, n]
             const float* __restrict__ l1_alpha, // [M]
             float* __restrict__ gpre_out,       // [M, B, n]
-            float* __restrict__ g_bias,         // [M, n]
+            float* __restrict__ gb_part,        // [M, nrg, n] per-32-row column sums
             int B, int d, int n, int prio, int gc_mode) {
   __shared__ float As[2][TBK * BMP];
   __shared__ float Bs[2][TBK * (TBN + 1)];
@@ -624,7 +626,12 @@ void k_gc_t(const float* __restrict__ r,        // [M, B, d]
 
   const EpiGeom g = epi_geom<NACC>();
   float* g_m = gpre_out + (long)m * B * n;
-  float* gb_m = g_bias + (long)m * n;
+  // bias grad: each wave owns one 32-row group of its columns and stores that
+  // group's column sum with a plain store; k_colsum_groups adds the groups in
+  // a fixed order (bitwise reproducible, unlike float atomics across blocks)
+  const int nrg = (B + 31) / 32;
+  const int rg = (row0 + g.wr) / 32;
+  float* gb_m = gb_part + ((long)m * nrg + rg) * n;
 
 #pragma unroll
   for (int tj = 0; tj < NACC; ++tj) {
@@ -652,8 +659,39 @@ void k_gc_t(const float* __restrict__ r,        // [M, B, d]
     if (col_ok && gc_mode == 0) {
       float other = __shfl_xor(colsum, 32, WAVE);
       float tot = colsum + other;
-      if (g.lane < 32 && tot != 0.f) atomicAdd(&gb_m[col], tot);
+      if (g.lane < 32 && rg < nrg) gb_m[col] = tot;
     }
+  }
+}
+
+// g_bias[m, col] (+)= sum over the nrg row groups of part[m, rg, col], in a
+// fixed order: 64 columns per block, the groups split into 4 contiguous slices
+// (one wave each, summed ascending), the 4 slice sums combined pairwise.
+extern "C" __global__ __launch_bounds__(256)
+void k_colsum_groups(const float* __restrict__ part,  // [M, nrg, n]
+                     float* __restrict__ g_bias,      // [M, n]
+                     int nrg, int n, long total,      // total = M * n
+                     int accumulate) {
+  __shared__ float sh[4][WAVE];
+  const int lc = threadIdx.x & (WAVE - 1);
+  const int sl = threadIdx.x / WAVE;
+  const long i = (long)blockIdx.x * WAVE + lc;
+  float s = 0.f;
+  if (i < total) {
+    const long m = i / n;
+    const int col = (int)(i - m * n);
+    const float* p = part + m * nrg * n + col;
+    const int per = (nrg + 3) / 4;
+    const int lo = sl * per;
+    const int hi = min(nrg, lo + per);
+#pragma unroll 16
+    for (int rg = lo; rg < hi; ++rg) s += p[(long)rg * n];
+  }
+  sh[sl][lc] = s;
+  __syncthreads();
+  if (sl == 0 && i < total) {
+    float t = (sh[0][lc] + sh[1][lc]) + (sh[2][lc] + sh[3][lc]);
+    g_bias[i] = accumulate ? g_bias[i] + t : t;
   }
 }
 

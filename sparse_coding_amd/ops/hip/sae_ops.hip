@@ -150,30 +150,47 @@ void dec_fwd(torch::Tensor c, torch::Tensor Wdec, torch::Tensor inv_norms,
 
 void gc(torch::Tensor r, torch::Tensor Wdec, torch::Tensor inv_norms,
         torch::Tensor c, torch::Tensor l1_alpha, torch::Tensor gpre,
-        torch::Tensor g_bias, int64_t bk, bool prio, int64_t gc_mode, int64_t bn) {
+        torch::Tensor g_bias, int64_t bk, bool prio, int64_t gc_mode, int64_t bn,
+        bool accumulate) {
   CHECK_IN(r); CHECK_IN(Wdec); CHECK_IN(inv_norms); CHECK_IN(c);
   CHECK_IN(l1_alpha); CHECK_IN(gpre); CHECK_IN(g_bias);
   int M = Wdec.size(0), n = Wdec.size(1), d = Wdec.size(2);
   int B = r.size(1);
   dim3 grid(cdiv(n, bn == 256 ? 256 : BN), cdiv(B, BM), M);
+  // gc_mode 0: the kernel stores one column sum per 32-row group; they are
+  // added into g_bias in a fixed order below (reproducible bias gradient);
+  // accumulate=false overwrites g_bias, so the caller need not zero it
+  const int nrg = cdiv(B, 32);
+  torch::Tensor part;
+  float* part_p = nullptr;
+  if (gc_mode == 0) {
+    TORCH_CHECK(g_bias.numel() == (long)M * n, "g_bias must be [M, n]");
+    part = torch::empty({M, nrg, n}, r.options());
+    part_p = part.data_ptr<float>();
+  }
   if (bn == 256)
     hipLaunchKernelGGL((k_gc_t<16, 4, 256>), grid, dim3(NTHREADS), 0, cur_stream(),
                        r.data_ptr<float>(), Wdec.data_ptr<float>(),
                        inv_norms.data_ptr<float>(), c.data_ptr<float>(),
                        l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
-                       g_bias.data_ptr<float>(), B, d, n, prio ? 1 : 0, (int)gc_mode);
+                       part_p, B, d, n, prio ? 1 : 0, (int)gc_mode);
   else if (bk == 16)
     hipLaunchKernelGGL((k_gc_t<16, 6>), grid, dim3(NTHREADS), 0, cur_stream(),
                        r.data_ptr<float>(), Wdec.data_ptr<float>(),
                        inv_norms.data_ptr<float>(), c.data_ptr<float>(),
                        l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
-                       g_bias.data_ptr<float>(), B, d, n, prio ? 1 : 0, (int)gc_mode);
+                       part_p, B, d, n, prio ? 1 : 0, (int)gc_mode);
   else
     hipLaunchKernelGGL((k_gc_t<32, 4>), grid, dim3(NTHREADS), 0, cur_stream(),
                        r.data_ptr<float>(), Wdec.data_ptr<float>(),
                        inv_norms.data_ptr<float>(), c.data_ptr<float>(),
                        l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
-                       g_bias.data_ptr<float>(), B, d, n, prio ? 1 : 0, (int)gc_mode);
+                       part_p, B, d, n, prio ? 1 : 0, (int)gc_mode);
+  if (gc_mode == 0) {
+    long total = (long)M * n;
+    hipLaunchKernelGGL(k_colsum_groups, dim3(cdiv(total, WAVE)), dim3(256), 0, cur_stream(),
+                       part_p, g_bias.data_ptr<float>(), nrg, n, total, accumulate ? 1 : 0);
+  }
 }
 
 void gc_thresh(torch::Tensor r, torch::Tensor Wdec, torch::Tensor inv_norms,
@@ -492,7 +509,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("r"), py::arg("Wdec"), py::arg("inv_norms"), py::arg("c"),
         py::arg("l1_alpha"), py::arg("gpre"), py::arg("g_bias"),
         py::arg("bk") = 32, py::arg("prio") = false, py::arg("gc_mode") = 0,
-        py::arg("bn") = 128);
+        py::arg("bn") = 128, py::arg("accumulate") = true);
   m.def("grad_w", &grad_w, "gw = beta*gw + alpha * P^T Q (batched over M)",
         py::arg("P"), py::arg("Q"), py::arg("gw"), py::arg("alpha"), py::arg("beta"),
         py::arg("bk") = 32, py::arg("prio") = false, py::arg("bn") = 128);

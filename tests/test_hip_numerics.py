@@ -140,6 +140,38 @@ def test_gc(shapes, kcfg):
     assert _rel_err(g_bias, ref.sum(dim=1)) < 1e-4
 
 
+def test_gc_bias_grad_reproducible(kcfg):
+    """The bias gradient is summed in a fixed order (per-32-row column sums,
+    then one ordered add): repeated calls give bitwise-identical g_bias, and
+    the sum is ADDED to what g_bias held.  B is no multiple of the 32-row
+    group nor of the 128-row tile, n no multiple of the column tile."""
+    ext = _ext()
+    M, B, d, n = 2, 300, 64, 200
+    torch.manual_seed(14)
+    r = torch.randn(M, B, d, device=DEV)
+    W = torch.randn(M, n, d, device=DEV)
+    c = torch.clamp(torch.randn(M, B, n, device=DEV), min=0)
+    l1 = torch.tensor([1e-3, 1e-2], device=DEV)
+    norms = torch.empty(M, n, device=DEV)
+    inv = torch.empty(M, n, device=DEV)
+    ext.row_norms(W, norms, inv, 1e-8)
+    outs = []
+    for _ in range(3):
+        gpre = torch.empty(M, B, n, device=DEV)
+        g_bias = torch.ones(M, n, device=DEV)
+        ext.gc(r, W, inv, c, l1, gpre, g_bias, kcfg["bk"], kcfg["prio"], bn=kcfg["bn"])
+        outs.append(g_bias)
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], outs[2])
+    # fp32 sum of 300 terms of magnitude ~gpre.abs().max(): a few ulp of the column's abs-sum
+    ref = 1.0 + gpre.double().sum(dim=1)
+    bound = 300 * 2.0 ** -24 * gpre.double().abs().sum(dim=1).max().item() + 2.0 ** -23
+    assert (outs[0].double() - ref).abs().max().item() <= bound
+    # accumulate=False overwrites whatever g_bias held
+    g_over = torch.full((M, n), 7.0, device=DEV)
+    ext.gc(r, W, inv, c, l1, gpre, g_over, kcfg["bk"], kcfg["prio"], bn=kcfg["bn"], accumulate=False)
+    assert (g_over.double() - (ref - 1.0)).abs().max().item() <= bound
+
+
 def test_grad_w(shapes, kcfg):
     ext = _ext()
     M, B, d, n = shapes["M"], shapes["B"], shapes["d"], shapes["n"]

@@ -77,18 +77,50 @@ def test_plot_scores(tmp_path):
     assert os.path.exists(tmp_path / "v.png")
 
 
+class _WordTok:
+    """Self-contained stand-in for an HF tokenizer (no hub download, no local
+    cache needed).  Words and punctuation marks are separate pieces; a word of
+    more than 6 letters splits into two pieces (so "library" is NOT a single
+    token and the single-token filter has something to reject).  Ids are
+    handed out in order of first appearance.  Covers the surface eval_prompts
+    uses: __call__ on a string or a list of strings, and vocab_size."""
+
+    vocab_size = 50257
+
+    def __init__(self):
+        self._ids = {}
+
+    def _encode(self, text):
+        import re
+
+        pieces = []
+        for w in re.findall(r"\w+|[^\w\s]", text):
+            pieces += [w] if len(w) <= 6 else [w[:4], "##" + w[4:]]
+        return [self._ids.setdefault(w, len(self._ids)) for w in pieces]
+
+    def __call__(self, text, add_special_tokens=False, padding=False):
+        if isinstance(text, str):
+            return {"input_ids": self._encode(text)}
+        return {"input_ids": [self._encode(t) for t in text]}
+
+
 def test_ioi_dataset():
-    from transformers import AutoTokenizer
+    from sparse_coding_amd.data.eval_prompts import (
+        PLACE_POOL,
+        filter_single_token,
+        generate_induction_dataset,
+        generate_ioi_dataset,
+    )
 
-    from sparse_coding_amd.data.eval_prompts import generate_induction_dataset, generate_ioi_dataset
-
-    try:
-        tok = AutoTokenizer.from_pretrained("gpt2")
-    except Exception:
-        pytest.skip("no tokenizer available offline")
+    tok = _WordTok()
+    # the filter drops the one place that is two tokens, keeps the rest in order
+    assert "library" in PLACE_POOL
+    assert filter_single_token(tok, PLACE_POOL) == [w for w in PLACE_POOL if w != "library"]
     clean, corr = generate_ioi_dataset(tok, 4, 4)
     assert clean.shape == corr.shape
     assert clean.shape[0] == 8
+    # a multi-token place would have made the rows ragged or shown up as its second piece
+    assert tok._ids["##ary"] not in clean.unique().tolist()
     ind = generate_induction_dataset(tok, 8, 16)
     assert torch.equal(ind[:, :8], ind[:, 8:])
 
