@@ -23,10 +23,31 @@ hand-written gfx950 HIP kernels (``sparse_coding_amd/ops/hip/sae_kernels.hip``):
 
 Fused-step coverage: EVERY trainable signature in the zoo — tied, untied,
 masked tied/untied, thresholding, reverse, tied-centered, positive-tied,
-TopK, LISTA, residual-denoising and semilinear.  The unrolled/MLP encoders
-(HipLISTAStep / HipResidualDenoisingStep / HipSemilinearStep) orchestrate
-the same MFMA GEMM kernels with hand-derived backward chains; elementwise
-glue runs as torch ops on persistent workspaces.
+TopK, LISTA, residual-denoising and semilinear.
+
+Structure.  Every step class derives from ``_HipStep``, which owns what
+does not depend on the signature: the Adam hyper-parameters, the kernel
+configuration resolved once per workspace allocation, the
+``grads_phase`` / ``update_phase`` / ``step`` protocol with hipGraph
+capture, and the two Adam launch helpers.  A class supplies its workspaces
+(``_alloc_workspaces``), its kernel sequence (``_grads``), its
+``update_phase`` and its ``_loss_data``.
+
+``HipSAEStep`` (tied, untied, masked, reverse) holds the
+transpose-in-staging launch chain ``_chain``: row norms -> enc_fwd ->
+dec_fwd -> gc -> the two grad_w GEMMs.  The centered, whitened and positive
+steps prepare their input (and dictionary), call that chain and add what is
+special to them; the thresholding step shares its weight-grad tail.  The
+pre-transposed (``staging="pre"``) pipeline is HipSAEStep's measured
+alternative to the chain.  The unrolled/MLP encoders (HipLISTAStep /
+HipResidualDenoisingStep / HipSemilinearStep) orchestrate the same MFMA GEMM
+kernels with hand-derived backward chains: LISTA fuses all its elementwise
+work into GEMM epilogues and one custom pass, the other two run their
+elementwise glue as torch ops on persistent workspaces.
+
+Every class replays its step from a captured hipGraph after two eager
+steps, except HipResidualDenoisingStep and HipSemilinearStep, which run
+eagerly.
 
 All GEMMs run on the exact-f32 MFMA path (v_mfma_f32_32x32x2_f32): fp32 end
 to end, the reference's training dtype.  Validated against the
@@ -39,12 +60,14 @@ overlaps with nothing locally but lands between grad GEMMs and Adam.
 
 from __future__ import annotations
 
+import os
 from typing import Optional
 
 import torch
 
 from sparse_coding_amd import ops as _ops
 from sparse_coding_amd.models import sae_signatures as sigs
+from sparse_coding_amd.ops.kconfig import kernel_config
 
 EPS_NORM = 1e-8
 
@@ -60,13 +83,11 @@ def _identity_centering(buffers) -> bool:
     return torch.equal(rot, eye) and bool((scale == 1).all()) and bool((trans == 0).all())
 
 
-def maybe_make_step(ensemble, required: bool = False) -> Optional["HipSAEStep"]:
-    """Return a HipSAEStep if (sig, device, buffers) are supported.
+def maybe_make_step(ensemble, required: bool = False) -> Optional["_HipStep"]:
+    """Return the fused step for (sig, device, buffers) if one exists.
 
     On a CUDA device with a supported signature, a missing extension is a
     hard error: GPU runs must not silently fall back to eager."""
-    import os
-
     if os.environ.get("SPARSE_CODING_AMD_FORCE_TORCH") == "1":
         return None
 
@@ -76,104 +97,66 @@ def maybe_make_step(ensemble, required: bool = False) -> Optional["HipSAEStep"]:
             raise RuntimeError(f"backend='hip' requested but ensemble device is {dev}")
         return None
 
-    sig = ensemble.sig
-    from sparse_coding_amd.models.topk import TopKEncoder
-
-    if sig is TopKEncoder:
-        ext = _ops.get_extension(required=True)
-        return HipTopKStep(ensemble, ext)
-
-    if sig is sigs.FunctionalThresholdingSAE:
-        ext = _ops.get_extension(required=True)
-        return HipThresholdStep(ensemble, ext)
-
-    if sig is sigs.FunctionalReverseSAE:
-        ext = _ops.get_extension(required=True)
-        return HipSAEStep(ensemble, ext, tied=True, reverse=True)
-
-    if sig is sigs.FunctionalTiedCenteredSAE:
-        ext = _ops.get_extension(required=True)
-        return HipCenteredStep(ensemble, ext)
-
-    from sparse_coding_amd.models.positive import FunctionalPositiveTiedSAE
-
-    if sig is FunctionalPositiveTiedSAE:
-        ext = _ops.get_extension(required=True)
-        return HipPositiveStep(ensemble, ext)
-
     from sparse_coding_amd.models.lista import (
         FunctionalLISTADenoisingSAE,
         FunctionalResidualDenoisingSAE,
     )
+    from sparse_coding_amd.models.positive import FunctionalPositiveTiedSAE
     from sparse_coding_amd.models.semilinear import SemiLinearSAE
+    from sparse_coding_amd.models.topk import TopKEncoder
 
-    if sig is FunctionalLISTADenoisingSAE:
-        ext = _ops.get_extension(required=True)
-        return HipLISTAStep(ensemble, ext)
-    if sig is FunctionalResidualDenoisingSAE:
-        ext = _ops.get_extension(required=True)
-        return HipResidualDenoisingStep(ensemble, ext)
-    if sig is SemiLinearSAE:
-        ext = _ops.get_extension(required=True)
-        return HipSemilinearStep(ensemble, ext)
+    def sae(**flags):
+        return lambda ens, ext: HipSAEStep(ens, ext, **flags)
 
-    if sig is sigs.FunctionalMaskedTiedSAE:
-        ext = _ops.get_extension(required=True)
-        return HipSAEStep(ensemble, ext, tied=True, masked=True)
-    if sig is sigs.FunctionalMaskedSAE:
-        ext = _ops.get_extension(required=True)
-        return HipSAEStep(ensemble, ext, tied=False, masked=True)
-
-    tied = sig is sigs.FunctionalTiedSAE
-    untied = sig is sigs.FunctionalSAE
-    if not (tied or untied):
+    make = {
+        TopKEncoder: HipTopKStep,
+        sigs.FunctionalThresholdingSAE: HipThresholdStep,
+        sigs.FunctionalReverseSAE: sae(tied=True, reverse=True),
+        sigs.FunctionalTiedCenteredSAE: HipCenteredStep,
+        FunctionalPositiveTiedSAE: HipPositiveStep,
+        FunctionalLISTADenoisingSAE: HipLISTAStep,
+        FunctionalResidualDenoisingSAE: HipResidualDenoisingStep,
+        SemiLinearSAE: HipSemilinearStep,
+        sigs.FunctionalMaskedTiedSAE: sae(tied=True, masked=True),
+        sigs.FunctionalMaskedSAE: sae(tied=False, masked=True),
+        sigs.FunctionalTiedSAE: sae(tied=True),
+        sigs.FunctionalSAE: sae(tied=False),
+    }.get(ensemble.sig)
+    if make is None:
         if required:
-            raise RuntimeError(f"backend='hip' requested but signature {sig.__name__} has no fused step yet")
+            raise RuntimeError(f"backend='hip' requested but signature {ensemble.sig.__name__} has no fused step yet")
         return None
-    if tied and not _identity_centering(ensemble.buffers):
+    if ensemble.sig is sigs.FunctionalTiedSAE and not _identity_centering(ensemble.buffers):
         # general affine whitening-centering (K7): PCA-whitened-input tied
         # SAE (reference sae_ensemble.py:98-132) — tied pipeline on a
         # precomputed per-model whitened input
-        ext = _ops.get_extension(required=True)
-        return HipWhitenedStep(ensemble, ext)
-
-    ext = _ops.get_extension(required=True)  # loud on GPU
-    return HipSAEStep(ensemble, ext, tied=tied)
+        make = HipWhitenedStep
+    return make(ensemble, _ops.get_extension(required=True))  # loud on GPU
 
 
-class HipSAEStep:
-    """Workspaces + kernel-sequence launcher for one ensemble."""
+def _announce(on_grads, *tensors):
+    if on_grads is not None:
+        on_grads(list(tensors))
 
-    def __init__(self, ensemble, ext, tied: bool, masked: bool = False, reverse: bool = False):
+
+class _HipStep:
+    """The signature-independent part of a fused step: hyper-parameters,
+    kernel configuration, the phase/step protocol with hipGraph capture,
+    and the Adam launch helpers."""
+
+    # replay the step from a captured hipGraph after two eager steps
+    captures_graph = True
+    # staging this class's kernels need; None -> honour the kernel config
+    staging = None
+    # the parameter whose [M, n, d] shape sizes the step
+    dict_key = "decoder"
+
+    def __init__(self, ensemble, ext):
         self.ens = ensemble
         self.ext = ext
-        self.tied = tied
-        self.masked = masked
-        # reverse SAE (sae_ensemble.py:447-503): code = pre * [pre+b > 0],
-        # |code| in the L1, sign-aware backward, NO bias gradient from the
-        # code path (only the L2-decay term moves the bias)
-        self.reverse = reverse
-
-        p = ensemble.params
-        self.n_models, self.n_dict, self.d_act = p["encoder"].shape
-        if not tied:
-            assert p["decoder"].shape == p["encoder"].shape
-
-        dev = p["encoder"].device
-        b = ensemble.buffers
-        self.l1_alpha = b["l1_alpha"].detach().to(dev, torch.float32).reshape(self.n_models).contiguous()
-        bd = b.get("bias_decay")
-        # the masked signatures carry a bias_decay buffer but never apply it
-        # (reference sae_ensemble.py:347-373,425-444) — force zero
-        if bd is None or masked:
-            bd = torch.zeros(self.n_models, device=dev)
-        self.bias_decay = bd.detach().to(dev, torch.float32).reshape(self.n_models).contiguous()
-        self.dict_sizes = None
-        if masked:
-            # K9: coefficient columns >= dict_size[m] are masked to zero in
-            # the encoder epilogue; every downstream grad is then zero via
-            # the c>0 gating, so the rest of the pipeline is unchanged
-            self.dict_sizes = b["dict_size"].detach().reshape(self.n_models).to(dev, torch.int32).contiguous()
+        W = ensemble.params[self.dict_key]
+        self.n_models, self.n_dict, self.d_act = W.shape
+        self._dev = W.device
 
         opt = ensemble.optimizer_kwargs
         self.lr = float(opt.get("lr", 1e-3))
@@ -184,181 +167,116 @@ class HipSAEStep:
         if name != "adam":
             raise RuntimeError(f"fused HIP step supports adam only, got {name}")
 
-        # per-feature lr multiplier for the post-resample warmup (Anthropic
-        # protocol): the resampler writes ramp values in place, the Adam
-        # kernels read it every step — allocated here (not in _alloc) so a
-        # batch-size change never resets an active warmup, and hipGraph
-        # capture sees a stable pointer
-        self.lr_mult = torch.ones(self.n_models, self.n_dict, device=dev)
+        l1 = ensemble.buffers.get("l1_alpha")  # TopK has no L1 term
+        if l1 is not None:
+            l1 = l1.detach().to(self._dev, torch.float32).reshape(self.n_models).contiguous()
+        self.l1_alpha = l1
+        self.zero_decay = torch.zeros(self.n_models, device=self._dev)
 
         # persistent workspaces, sized lazily on first batch
         self._B = None
         # hipGraph capture of the whole step (single-GPU path): replayed
         # after 2 eager warmup steps; disabled via SPARSE_CODING_AMD_NO_GRAPH=1
-        import os as _os
-
-        self.use_graph = _os.environ.get("SPARSE_CODING_AMD_NO_GRAPH") != "1"
+        self.use_graph = self.captures_graph and os.environ.get("SPARSE_CODING_AMD_NO_GRAPH") != "1"
         self._graph = None
         self._eager_steps = 0
 
     # -- workspace management -------------------------------------------------
-    def _alloc(self, B: int):
-        from sparse_coding_amd.ops.kconfig import kernel_config
+    def _empty(self, *shape):
+        return torch.empty(shape, device=self._dev, dtype=torch.float32)
 
-        self.kc = kernel_config()
-        M, n, d = self.n_models, self.n_dict, self.d_act
-        dev = self.ens.params["encoder"].device
-        f = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
-        self.c = f(M, B, n)
-        self.gpre = f(M, B, n)
-        self.r = f(M, B, d)
-        self.norms = f(M, n)
-        self.inv_norms = f(M, n)
-        self.loss_parts = f(M, 2)
-        self.fired = torch.zeros(M, n, device=dev)
-        self.g_bias = f(M, n)
-        self.gw = f(M, n, d)
-        if self.reverse:
-            self.kc["staging"] = "t"
-        if self.kc["staging"] == "pre":
-            # pre-transposed operands: every GEMM's staging direct/b128
-            self.xT = f(d, B)
-            self.rT = f(M, d, B)
-            self.WT = f(M, d, n)
-            if not self.tied:
-                self.WencT = f(M, d, n)
-        if not self.tied:
-            self.gw_enc = f(M, n, d)
+    def _zeros(self, *shape):
+        return torch.zeros(shape, device=self._dev, dtype=torch.float32)
+
+    def _ones(self, *shape):
+        return torch.ones(shape, device=self._dev, dtype=torch.float32)
+
+    def _alloc(self, B: int):
+        kc = kernel_config()
+        if self.staging is not None:
+            kc["staging"] = self.staging
+        self.kc = kc
+        # tile parameters, resolved once: per-kernel overrides fall back to
+        # the global tile depth / width
+        self.bk, self.prio, self.bn = kc["bk"], kc["prio"], kc["bn"]
+        self.bn_enc = kc["bn_enc"] or self.bn
+        self.bk_dec = kc["bk_dec"] or self.bk
+        self.bk_gw = kc["bk_grad_w"] or self.bk
+        self._alloc_workspaces(B)
         self._B = B
         self._graph = None
         self._eager_steps = 0
 
+    def _alloc_workspaces(self, B: int):
+        raise NotImplementedError
+
     # -- phases ---------------------------------------------------------------
     def grads_phase(self, x: torch.Tensor, on_grads=None):
-        """Forward + backward: fills self.gw (+gw_enc), g_bias, loss parts.
+        """Forward + backward: fills the gradient workspaces and loss parts.
 
         on_grads: optional callback(list_of_tensors) fired as gradient
         tensors become final — used by the DP trainer to launch RCCL
-        all-reduces that overlap the remaining grad GEMMs (the [M,n,d]
-        weight grads are chunked over model halves for this).
+        all-reduces that overlap the remaining grad GEMMs.  Over one call it
+        is handed every tensor of dp_grad_tensors() exactly once (whole, or
+        as disjoint slices along dim 0).
         """
-        ens, ext = self.ens, self.ext
-        M, n, d = self.n_models, self.n_dict, self.d_act
         B = x.shape[0]
         if self._B != B:
             self._alloc(B)
-
-        x = x.contiguous()
-        p = ens.params
-        enc = p["encoder"]
-        bias = p["encoder_bias"]
-        dict_w = enc if self.tied else p["decoder"]
-
-        self.loss_parts.zero_()
-        if self.reverse or self.kc["staging"] == "pre":
-            self.g_bias.zero_()  # else k_gc overwrites it (accumulate=False)
-        self._fired_step = self.fired  # accumulated across steps for resampling
-
-        kc = self.kc
-        bk, prio = kc["bk"], kc["prio"]
-        bn = kc.get("bn", 128)
-        bn_enc = kc.get("bn_enc") or bn
-        bk_dec = kc["bk_dec"] or bk
-        bk_gw = kc["bk_grad_w"] or bk
-
-        ext.row_norms(dict_w, self.norms, self.inv_norms, EPS_NORM)
-        if kc["staging"] == "pre":
-            # pre-transpose once per step so the big GEMMs stage all operands
-            # directly (b128 LDS writes): x^T, What^T (inv-norm pre-applied)
-            ext.transpose_scale(x, self.xT, None)
-            ext.transpose_scale(dict_w, self.WT, self.inv_norms)
-            if self.tied:
-                ext.enc_fwd2(self.xT, self.WT, bias, self.c, self.loss_parts, self.fired, 0, bk, prio,
-                             dict_sizes=self.dict_sizes)
-            else:
-                ext.transpose_scale(enc, self.WencT, None)
-                ext.enc_fwd2(self.xT, self.WencT, bias, self.c, self.loss_parts, self.fired, 0, bk, prio,
-                             dict_sizes=self.dict_sizes)
-            ext.dec_fwd(self.c, dict_w, self.inv_norms, x, self.r, self.loss_parts, bk_dec, prio)
-            ext.transpose_scale(self.r, self.rT, None)
-            ext.gc2(self.rT, self.WT, self.c, self.l1_alpha, self.gpre, self.g_bias, bk, prio)
-        else:
-            # transpose-in-staging GEMMs (no separate transpose kernels)
-            enc_inv = self.inv_norms if self.tied else None
-            mode = 3 if self.reverse else 0
-            ext.enc_fwd(x, enc, bias, enc_inv, self.c, self.loss_parts, self.fired, mode, bk, prio, bn_enc,
-                        dict_sizes=self.dict_sizes)
-            ext.dec_fwd(self.c, dict_w, self.inv_norms, x, self.r, self.loss_parts, bk_dec, prio, bn)
-            ext.gc(self.r, dict_w, self.inv_norms, self.c, self.l1_alpha, self.gpre, self.g_bias, bk, prio,
-                   gc_mode=1 if self.reverse else 0, bn=bn_enc, accumulate=False)
-
-        if on_grads is not None:
-            on_grads([self.g_bias])  # final after k_gc
-
-        gscale = 2.0 / (B * d)
-        if self.tied and on_grads is not None and M > 1:
-            # chunk the weight-grad GEMMs over model groups so each chunk's
-            # all-reduce rides under the next chunk's compute; quarters keep
-            # the exposed tail to one chunk's reduce (xGMI ring: ~2*S*7/8 /
-            # 153 GB/s per link for an S-byte chunk)
-            n_chunks = min(M, 4)
-            bounds = [M * i // n_chunks for i in range(n_chunks + 1)]
-            for lo, hi in zip(bounds[:-1], bounds[1:]):
-                sl = slice(lo, hi)
-                ext.grad_w(self.c[sl], self.r[sl], self.gw[sl], gscale, 0.0, bk_gw, prio, bn)
-                ext.grad_w(self.gpre[sl], x, self.gw[sl], 1.0, 1.0, bk_gw, prio, bn)
-                on_grads([self.gw[sl]])
-        elif self.tied:
-            ext.grad_w(self.c, self.r, self.gw, gscale, 0.0, bk_gw, prio, bn)
-            ext.grad_w(self.gpre, x, self.gw, 1.0, 1.0, bk_gw, prio, bn)
-            if on_grads is not None:  # M == 1: single unchunked grad tensor
-                on_grads([self.gw])
-        else:
-            ext.grad_w(self.c, self.r, self.gw, gscale, 0.0, bk_gw, prio, bn)
-            if on_grads is not None:
-                on_grads([self.gw])
-            ext.grad_w(self.gpre, x, self.gw_enc, 1.0, 0.0, bk_gw, prio, bn)
-            if on_grads is not None:
-                on_grads([self.gw_enc])
+        self._grads(x.contiguous(), B, on_grads)
         return B
 
-    def update_phase(self, B: int):
-        """Adam updates (projection through the renorm for the dictionary)."""
-        ens, ext = self.ens, self.ext
-        st = ens.optim_states
-        st["step"] += 1.0
-        step_no = st["step"]
-        p = ens.params
+    def _grads(self, x: torch.Tensor, B: int, on_grads):
+        raise NotImplementedError
 
-        if self.tied:
-            ext.project_adam(p["encoder"], self.gw, self.norms,
-                             st["mu"]["encoder"], st["nu"]["encoder"], step_no,
-                             self.n_dict, self.lr, self.beta1, self.beta2,
-                             self.eps, EPS_NORM, True, lr_mult=self.lr_mult)
-        else:
-            ext.project_adam(p["decoder"], self.gw, self.norms,
-                             st["mu"]["decoder"], st["nu"]["decoder"], step_no,
-                             self.n_dict, self.lr, self.beta1, self.beta2,
-                             self.eps, EPS_NORM, True, lr_mult=self.lr_mult)
-            ext.project_adam(p["encoder"], self.gw_enc, self.norms,
-                             st["mu"]["encoder"], st["nu"]["encoder"], step_no,
-                             self.n_dict, self.lr, self.beta1, self.beta2,
-                             self.eps, EPS_NORM, False, lr_mult=self.lr_mult)
-        ext.bias_adam(p["encoder_bias"], self.g_bias, self.bias_decay,
-                      st["mu"]["encoder_bias"], st["nu"]["encoder_bias"],
-                      step_no, self.lr, self.beta1, self.beta2, self.eps,
-                      lr_mult=self.lr_mult)
+    def update_phase(self, B: int):
+        raise NotImplementedError
 
     def _loss_data(self, B: int):
-        d = self.d_act
-        mse = self.loss_parts[:, 0] / (B * d)
-        l1 = self.l1_alpha * self.loss_parts[:, 1] / B
-        if self.masked:  # masked losses carry no bias-decay term
-            return {"loss": mse + l1, "l_reconstruction": mse, "l_l1": l1}
-        bias = self.ens.params["encoder_bias"]
-        l_bd = self.bias_decay * torch.norm(bias, 2, dim=-1)
-        total = mse + l1 + l_bd
-        return {"loss": total, "l_reconstruction": mse, "l_l1": l1, "l_bias_decay": l_bd}
+        raise NotImplementedError
+
+    def dp_grad_tensors(self):
+        """Tensors to all-reduce for data parallelism (average across ranks)."""
+        raise NotImplementedError
+
+    @property
+    def codes(self):
+        """The [M, B, n] codes of the last step (returned as aux["c"])."""
+        return self.c
+
+    def _mse_l1_loss(self, B: int, l1_sum):
+        mse = self.loss_parts[:, 0] / (B * self.d_act)
+        l1 = self.l1_alpha * l1_sum / B
+        return {"loss": mse + l1, "l_reconstruction": mse, "l_l1": l1}
+
+    # -- Adam launches --------------------------------------------------------
+    def _begin_update(self):
+        st = self.ens.optim_states
+        st["step"] += 1.0
+        return st["step"]
+
+    def _param_state(self, key):
+        """(param, mu, nu) at a key path: "encoder" or ("encoder_layers", l, "W")."""
+        st = self.ens.optim_states
+        p, mu, nu = self.ens.params, st["mu"], st["nu"]
+        for k in (key,) if isinstance(key, str) else key:
+            p, mu, nu = p[k], mu[k], nu[k]
+        return p, mu, nu
+
+    def _adam_matrix(self, key, grad, step_no, project, n_per_model=None, lr_mult=None,
+                     w_used=None, clamp_mask=False, eps_norm=EPS_NORM):
+        """Adam on a matrix parameter; project=True first pushes the gradient
+        through the in-forward row renormalization (k_project_adam)."""
+        W, mu, nu = self._param_state(key)
+        self.ext.project_adam(W, grad, self.norms, mu, nu, step_no, n_per_model or self.n_dict,
+                              self.lr, self.beta1, self.beta2, self.eps, eps_norm, project,
+                              w_used=w_used, clamp_mask=clamp_mask, lr_mult=lr_mult)
+
+    def _adam_vector(self, key, grad, step_no, decay=None, lr_mult=None):
+        """Adam on an [M, k] vector parameter (+ L2-decay gradient)."""
+        v, mu, nu = self._param_state(key)
+        self.ext.bias_adam(v, grad, self.zero_decay if decay is None else decay, mu, nu, step_no,
+                           self.lr, self.beta1, self.beta2, self.eps, lr_mult=lr_mult)
 
     # -- public ---------------------------------------------------------------
     def _capture(self, x: torch.Tensor) -> None:
@@ -385,14 +303,179 @@ class HipSAEStep:
             if self._graph is not None:
                 self.x_static.copy_(minibatches)
                 self._graph.replay()
-                return self._loss_data(B), {"c": self.c}
+                return self._loss_data(B), {"c": self.codes}
         B = self.grads_phase(minibatches)
         self.update_phase(B)
         self._eager_steps += 1
-        return self._loss_data(B), {"c": self.c}
+        return self._loss_data(B), {"c": self.codes}
+
+
+class HipSAEStep(_HipStep):
+    """Workspaces + kernel-sequence launcher for the plain SAE family:
+    tied, untied, masked and reverse."""
+
+    dict_key = "encoder"
+
+    def __init__(self, ensemble, ext, tied: bool, masked: bool = False, reverse: bool = False):
+        super().__init__(ensemble, ext)
+        self.tied = tied
+        self.masked = masked
+        # reverse SAE (sae_ensemble.py:447-503): code = pre * [pre+b > 0],
+        # |code| in the L1, sign-aware backward, NO bias gradient from the
+        # code path (only the L2-decay term moves the bias)
+        self.reverse = reverse
+        if reverse:
+            self.staging = "t"  # the reverse epilogues exist only there
+
+        p = ensemble.params
+        if not tied:
+            assert p["decoder"].shape == p["encoder"].shape
+
+        dev = self._dev
+        b = ensemble.buffers
+        bd = b.get("bias_decay")
+        # the masked signatures carry a bias_decay buffer but never apply it
+        # (reference sae_ensemble.py:347-373,425-444) — force zero
+        if bd is None or masked:
+            bd = torch.zeros(self.n_models, device=dev)
+        self.bias_decay = bd.detach().to(dev, torch.float32).reshape(self.n_models).contiguous()
+        self.dict_sizes = None
+        if masked:
+            # K9: coefficient columns >= dict_size[m] are masked to zero in
+            # the encoder epilogue; every downstream grad is then zero via
+            # the c>0 gating, so the rest of the pipeline is unchanged
+            self.dict_sizes = b["dict_size"].detach().reshape(self.n_models).to(dev, torch.int32).contiguous()
+
+        # per-feature lr multiplier for the post-resample warmup (Anthropic
+        # protocol): the resampler writes ramp values in place, the Adam
+        # kernels read it every step — allocated here (not in _alloc) so a
+        # batch-size change never resets an active warmup, and hipGraph
+        # capture sees a stable pointer
+        self.lr_mult = torch.ones(self.n_models, self.n_dict, device=dev)
+
+    def _alloc_workspaces(self, B: int):
+        M, n, d = self.n_models, self.n_dict, self.d_act
+        f = self._empty
+        self.c = f(M, B, n)
+        self.gpre = f(M, B, n)
+        self.r = f(M, B, d)
+        self.norms = f(M, n)
+        self.inv_norms = f(M, n)
+        self.loss_parts = f(M, 2)
+        self.fired = self._zeros(M, n)  # accumulated across steps for resampling
+        self.g_bias = f(M, n)
+        self.gw = f(M, n, d)
+        if self.kc["staging"] == "pre":
+            # pre-transposed operands: every GEMM's staging direct/b128
+            self.xT = f(d, B)
+            self.rT = f(M, d, B)
+            self.WT = f(M, d, n)
+            if not self.tied:
+                self.WencT = f(M, d, n)
+        if not self.tied:
+            self.gw_enc = f(M, n, d)
+
+    def _grads(self, x, B, on_grads):
+        p = self.ens.params
+        bias = p["encoder_bias"]
+        dict_w = p["encoder"] if self.tied else p["decoder"]
+        self.loss_parts.zero_()
+        if self.kc["staging"] != "pre":
+            self._chain(x, dict_w, bias, enc_mode=3 if self.reverse else 0,
+                        gc_mode=1 if self.reverse else 0, on_grads=on_grads)
+            return
+
+        # pre-transpose once per step so the big GEMMs stage all operands
+        # directly (b128 LDS writes): x^T, What^T (inv-norm pre-applied)
+        ext, bk, prio = self.ext, self.bk, self.prio
+        self.g_bias.zero_()  # k_gc2 accumulates into it
+        ext.row_norms(dict_w, self.norms, self.inv_norms, EPS_NORM)
+        ext.transpose_scale(x, self.xT, None)
+        ext.transpose_scale(dict_w, self.WT, self.inv_norms)
+        WencT = self.WT
+        if not self.tied:
+            WencT = self.WencT
+            ext.transpose_scale(p["encoder"], WencT, None)
+        ext.enc_fwd2(self.xT, WencT, bias, self.c, self.loss_parts, self.fired, 0, bk, prio,
+                     dict_sizes=self.dict_sizes)
+        ext.dec_fwd(self.c, dict_w, self.inv_norms, x, self.r, self.loss_parts, self.bk_dec, prio)
+        ext.transpose_scale(self.r, self.rT, None)
+        ext.gc2(self.rT, self.WT, self.c, self.l1_alpha, self.gpre, self.g_bias, bk, prio)
+        _announce(on_grads, self.g_bias)
+        self._weight_grads(x, B, on_grads)
+
+    def _chain(self, x, dict_w, bias, enc_mode=0, gc_mode=0, on_grads=None):
+        """The transpose-in-staging launch chain (no separate transpose
+        kernels): row norms -> enc_fwd -> dec_fwd -> gc -> weight grads.
+
+        x is the input the pipeline sees, shared [B, d] or per-model
+        [M, B, d]; dict_w the dictionary it runs on (the tied encoder, a
+        clamped copy of it, or the untied decoder).  With on_grads the
+        gradients are announced as they become final (g_bias after k_gc, the
+        weight grads in chunks); without it the caller announces them."""
+        ext, bk, prio = self.ext, self.bk, self.prio
+        B = x.shape[-2]
+        enc, enc_inv = (dict_w, self.inv_norms) if self.tied else (self.ens.params["encoder"], None)
+        if gc_mode == 1:
+            self.g_bias.zero_()  # the reverse k_gc writes no bias gradient
+        ext.row_norms(dict_w, self.norms, self.inv_norms, EPS_NORM)
+        ext.enc_fwd(x, enc, bias, enc_inv, self.c, self.loss_parts, self.fired, enc_mode, bk, prio,
+                    self.bn_enc, dict_sizes=self.dict_sizes)
+        ext.dec_fwd(self.c, dict_w, self.inv_norms, x, self.r, self.loss_parts, self.bk_dec, prio, self.bn)
+        # gc_mode 0 overwrites g_bias (accumulate=False): no memset needed
+        ext.gc(self.r, dict_w, self.inv_norms, self.c, self.l1_alpha, self.gpre, self.g_bias, bk, prio,
+               gc_mode=gc_mode, bn=self.bn_enc, accumulate=False)
+        _announce(on_grads, self.g_bias)  # final after k_gc
+        self._weight_grads(x, B, on_grads)
+
+    def _weight_grads(self, x, B, on_grads=None):
+        """gw = gscale c^T r (+ gpre^T x when tied, else gw_enc = gpre^T x)."""
+        ext, prio, bn, bk_gw = self.ext, self.prio, self.bn, self.bk_gw
+        M = self.n_models
+        gscale = 2.0 / (B * self.d_act)
+        if self.tied and on_grads is not None and M > 1:
+            # chunk the weight-grad GEMMs over model groups so each chunk's
+            # all-reduce rides under the next chunk's compute; quarters keep
+            # the exposed tail to one chunk's reduce (xGMI ring: ~2*S*7/8 /
+            # 153 GB/s per link for an S-byte chunk)
+            n_chunks = min(M, 4)
+            bounds = [M * i // n_chunks for i in range(n_chunks + 1)]
+            for lo, hi in zip(bounds[:-1], bounds[1:]):
+                sl = slice(lo, hi)
+                ext.grad_w(self.c[sl], self.r[sl], self.gw[sl], gscale, 0.0, bk_gw, prio, bn)
+                ext.grad_w(self.gpre[sl], x[sl] if x.dim() == 3 else x, self.gw[sl], 1.0, 1.0, bk_gw, prio, bn)
+                on_grads([self.gw[sl]])
+        elif self.tied:
+            ext.grad_w(self.c, self.r, self.gw, gscale, 0.0, bk_gw, prio, bn)
+            ext.grad_w(self.gpre, x, self.gw, 1.0, 1.0, bk_gw, prio, bn)
+            _announce(on_grads, self.gw)  # M == 1: single unchunked grad tensor
+        else:
+            ext.grad_w(self.c, self.r, self.gw, gscale, 0.0, bk_gw, prio, bn)
+            _announce(on_grads, self.gw)
+            ext.grad_w(self.gpre, x, self.gw_enc, 1.0, 0.0, bk_gw, prio, bn)
+            _announce(on_grads, self.gw_enc)
+
+    def update_phase(self, B: int):
+        """Adam updates (projection through the renorm for the dictionary)."""
+        t = self._begin_update()
+        if self.tied:
+            self._adam_matrix("encoder", self.gw, t, project=True, lr_mult=self.lr_mult)
+        else:
+            self._adam_matrix("decoder", self.gw, t, project=True, lr_mult=self.lr_mult)
+            self._adam_matrix("encoder", self.gw_enc, t, project=False, lr_mult=self.lr_mult)
+        self._adam_vector("encoder_bias", self.g_bias, t, decay=self.bias_decay, lr_mult=self.lr_mult)
+
+    def _loss_data(self, B: int):
+        out = self._mse_l1_loss(B, self.loss_parts[:, 1])
+        if self.masked:  # masked losses carry no bias-decay term
+            return out
+        bias = self.ens.params["encoder_bias"]
+        l_bd = self.bias_decay * torch.norm(bias, 2, dim=-1)
+        out["loss"] = out["loss"] + l_bd
+        out["l_bias_decay"] = l_bd
+        return out
 
     def dp_grad_tensors(self):
-        """Tensors to all-reduce for data parallelism (average across ranks)."""
         ts = [self.gw, self.g_bias]
         if not self.tied:
             ts.append(self.gw_enc)
@@ -407,76 +490,36 @@ class HipCenteredStep(HipSAEStep):
         dL/dt = gscale * sum_b r_b  -  g_bias @ What
     (g_bias is the column sum of gpre from k_gc)."""
 
+    staging = "t"  # the per-model-x-stride kernels live in the "t" path
+
     def __init__(self, ensemble, ext):
         super().__init__(ensemble, ext, tied=True)
 
-    def _alloc(self, B: int):
-        super()._alloc(B)
-        M, n, d = self.n_models, self.n_dict, self.d_act
-        dev = self.ens.params["encoder"].device
-        self.xc = torch.empty(M, B, d, device=dev)
-        self.g_center = torch.empty(M, d, device=dev)
-        self.zero_decay = torch.zeros_like(self.bias_decay)
-        self.kc["staging"] = "t"
+    def _alloc_workspaces(self, B: int):
+        super()._alloc_workspaces(B)
+        self.xc = self._empty(self.n_models, B, self.d_act)
+        self.g_center = self._empty(self.n_models, self.d_act)
 
-    def grads_phase(self, x: torch.Tensor, on_grads=None):
-        ens, ext = self.ens, self.ext
-        B = x.shape[0]
-        if self._B != B:
-            self._alloc(B)
-        x = x.contiguous()
-        p = ens.params
+    def _grads(self, x, B, on_grads):
+        p = self.ens.params
         enc = p["encoder"]
-        bias = p["encoder_bias"]
-        center = p["center"]
-        bk, prio = self.kc["bk"], self.kc["prio"]
-        bk_gw = self.kc["bk_grad_w"] or bk
-
         self.loss_parts.zero_()
-        self.g_bias.zero_()
-
-        torch.sub(x.unsqueeze(0), center.unsqueeze(1), out=self.xc)
-        ext.row_norms(enc, self.norms, self.inv_norms, EPS_NORM)
-        ext.enc_fwd(self.xc, enc, bias, self.inv_norms, self.c,
-                    self.loss_parts, self.fired, 0, bk, prio)
-        ext.dec_fwd(self.c, enc, self.inv_norms, self.xc, self.r,
-                    self.loss_parts, self.kc["bk_dec"] or bk, prio)
-        ext.gc(self.r, enc, self.inv_norms, self.c, self.l1_alpha,
-               self.gpre, self.g_bias, bk, prio)
-
-        gscale = 2.0 / (B * self.d_act)
-        ext.grad_w(self.c, self.r, self.gw, gscale, 0.0, bk_gw, prio)
-        ext.grad_w(self.gpre, self.xc, self.gw, 1.0, 1.0, bk_gw, prio)
+        torch.sub(x.unsqueeze(0), p["center"].unsqueeze(1), out=self.xc)
+        self._chain(self.xc, enc, p["encoder_bias"])
         # center gradient from existing reductions (docstring derivation);
         # column sum via the coalesced k_colsum kernel
-        ext.colsum(self.r, self.g_center, gscale)
+        self.ext.colsum(self.r, self.g_center, 2.0 / (B * self.d_act))
         self.g_center.sub_(torch.einsum("mn,mnd->md", self.g_bias * self.inv_norms, enc))
-        if on_grads is not None:
-            on_grads([self.gw, self.g_bias, self.g_center])
-        return B
+        _announce(on_grads, self.gw, self.g_bias, self.g_center)
 
     def update_phase(self, B: int):
-        ens, ext = self.ens, self.ext
-        st = ens.optim_states
-        st["step"] += 1.0
-        step_no = st["step"]
-        p = ens.params
-        ext.project_adam(p["encoder"], self.gw, self.norms,
-                         st["mu"]["encoder"], st["nu"]["encoder"], step_no,
-                         self.n_dict, self.lr, self.beta1, self.beta2,
-                         self.eps, EPS_NORM, True, lr_mult=self.lr_mult)
-        ext.bias_adam(p["encoder_bias"], self.g_bias, self.zero_decay,
-                      st["mu"]["encoder_bias"], st["nu"]["encoder_bias"],
-                      step_no, self.lr, self.beta1, self.beta2, self.eps,
-                      lr_mult=self.lr_mult)
-        ext.bias_adam(p["center"], self.g_center, self.zero_decay,
-                      st["mu"]["center"], st["nu"]["center"],
-                      step_no, self.lr, self.beta1, self.beta2, self.eps)
+        t = self._begin_update()
+        self._adam_matrix("encoder", self.gw, t, project=True, lr_mult=self.lr_mult)
+        self._adam_vector("encoder_bias", self.g_bias, t, lr_mult=self.lr_mult)
+        self._adam_vector("center", self.g_center, t)
 
     def _loss_data(self, B: int):
-        mse = self.loss_parts[:, 0] / (B * self.d_act)
-        l1 = self.l1_alpha * self.loss_parts[:, 1] / B
-        return {"loss": mse + l1, "l_reconstruction": mse, "l_l1": l1}
+        return self._mse_l1_loss(B, self.loss_parts[:, 1])
 
     def dp_grad_tensors(self):
         return [self.gw, self.g_bias, self.g_center]
@@ -493,6 +536,8 @@ class HipWhitenedStep(HipSAEStep):
     model-stride kernels as HipCenteredStep) after ONE batched [d, d] GEMM:
     x' = (x - t) @ Wc with Wc = (rot * s[:, None])^T precomputed."""
 
+    staging = "t"  # the per-model-x-stride kernels live in the "t" path
+
     def __init__(self, ensemble, ext):
         super().__init__(ensemble, ext, tied=True)
         b = ensemble.buffers
@@ -502,47 +547,18 @@ class HipWhitenedStep(HipSAEStep):
         # result[b, c] = sum_u (x-t)[b, u] * rot[c, u] * s[c]
         self.Wc = (rot * scale.unsqueeze(-1)).transpose(1, 2).contiguous()  # [M, d, d]
 
-    def _alloc(self, B: int):
-        super()._alloc(B)
-        M, n, d = self.n_models, self.n_dict, self.d_act
-        dev = self.ens.params["encoder"].device
-        self.xsub = torch.empty(M, B, d, device=dev)
-        self.xc = torch.empty(M, B, d, device=dev)
-        # the per-model-x-stride kernels live in the "t" staging path
-        self.kc["staging"] = "t"
+    def _alloc_workspaces(self, B: int):
+        super()._alloc_workspaces(B)
+        self.xsub = self._empty(self.n_models, B, self.d_act)
+        self.xc = self._empty(self.n_models, B, self.d_act)
 
-    def grads_phase(self, x: torch.Tensor, on_grads=None):
-        ens, ext = self.ens, self.ext
-        B = x.shape[0]
-        if self._B != B:
-            self._alloc(B)
-        x = x.contiguous()
-        p = ens.params
-        enc = p["encoder"]
-        bias = p["encoder_bias"]
-        bk, prio = self.kc["bk"], self.kc["prio"]
-        bk_gw = self.kc["bk_grad_w"] or bk
-
+    def _grads(self, x, B, on_grads):
+        p = self.ens.params
         self.loss_parts.zero_()
-        self.g_bias.zero_()
-
         torch.sub(x.unsqueeze(0), self.trans.unsqueeze(1), out=self.xsub)
         torch.bmm(self.xsub, self.Wc, out=self.xc)  # library GEMM: plain batched matmul
-
-        ext.row_norms(enc, self.norms, self.inv_norms, EPS_NORM)
-        ext.enc_fwd(self.xc, enc, bias, self.inv_norms, self.c,
-                    self.loss_parts, self.fired, 0, bk, prio)
-        ext.dec_fwd(self.c, enc, self.inv_norms, self.xc, self.r,
-                    self.loss_parts, self.kc["bk_dec"] or bk, prio)
-        ext.gc(self.r, enc, self.inv_norms, self.c, self.l1_alpha,
-               self.gpre, self.g_bias, bk, prio)
-
-        gscale = 2.0 / (B * self.d_act)
-        ext.grad_w(self.c, self.r, self.gw, gscale, 0.0, bk_gw, prio)
-        ext.grad_w(self.gpre, self.xc, self.gw, 1.0, 1.0, bk_gw, prio)
-        if on_grads is not None:
-            on_grads([self.gw, self.g_bias])
-        return B
+        self._chain(self.xc, p["encoder"], p["encoder_bias"])
+        _announce(on_grads, self.gw, self.g_bias)
     # update_phase / _loss_data: inherited tied versions (incl. bias decay)
 
 
@@ -552,66 +568,31 @@ class HipPositiveStep(HipSAEStep):
     x' = x + 0.18; the projected gradient is masked by the clamp derivative
     before Adam updates the raw (signed) encoder."""
 
+    staging = "t"
+
     def __init__(self, ensemble, ext):
         super().__init__(ensemble, ext, tied=True)
 
-    def _alloc(self, B: int):
-        super()._alloc(B)
-        M, n, d = self.n_models, self.n_dict, self.d_act
-        dev = self.ens.params["encoder"].device
-        self.Wc = torch.empty(M, n, d, device=dev)
-        self.x_shift = torch.empty(B, d, device=dev)
-        self.kc["staging"] = "t"
+    def _alloc_workspaces(self, B: int):
+        super()._alloc_workspaces(B)
+        self.Wc = self._empty(self.n_models, self.n_dict, self.d_act)
+        self.x_shift = self._empty(B, self.d_act)
 
-    def grads_phase(self, x: torch.Tensor, on_grads=None):
+    def _grads(self, x, B, on_grads):
         from sparse_coding_amd.models.positive import INPUT_SHIFT
 
-        ens, ext = self.ens, self.ext
-        B = x.shape[0]
-        if self._B != B:
-            self._alloc(B)
-        x = x.contiguous()
-        p = ens.params
-        enc = p["encoder"]
-        bias = p["encoder_bias"]
-        bk, prio = self.kc["bk"], self.kc["prio"]
-        bk_gw = self.kc["bk_grad_w"] or bk
-
+        p = self.ens.params
         self.loss_parts.zero_()
-        self.g_bias.zero_()
-
-        torch.clamp(enc, min=0.0, out=self.Wc)
+        torch.clamp(p["encoder"], min=0.0, out=self.Wc)
         torch.add(x, INPUT_SHIFT, out=self.x_shift)
-        ext.row_norms(self.Wc, self.norms, self.inv_norms, EPS_NORM)
-        ext.enc_fwd(self.x_shift, self.Wc, bias, self.inv_norms, self.c,
-                    self.loss_parts, self.fired, 0, bk, prio)
-        ext.dec_fwd(self.c, self.Wc, self.inv_norms, self.x_shift, self.r,
-                    self.loss_parts, self.kc["bk_dec"] or bk, prio)
-        ext.gc(self.r, self.Wc, self.inv_norms, self.c, self.l1_alpha,
-               self.gpre, self.g_bias, bk, prio)
-
-        gscale = 2.0 / (B * self.d_act)
-        ext.grad_w(self.c, self.r, self.gw, gscale, 0.0, bk_gw, prio)
-        ext.grad_w(self.gpre, self.x_shift, self.gw, 1.0, 1.0, bk_gw, prio)
-        if on_grads is not None:
-            on_grads([self.gw, self.g_bias])
-        return B
+        self._chain(self.x_shift, self.Wc, p["encoder_bias"])
+        _announce(on_grads, self.gw, self.g_bias)
 
     def update_phase(self, B: int):
-        ens, ext = self.ens, self.ext
-        st = ens.optim_states
-        st["step"] += 1.0
-        step_no = st["step"]
-        p = ens.params
-        ext.project_adam(p["encoder"], self.gw, self.norms,
-                         st["mu"]["encoder"], st["nu"]["encoder"], step_no,
-                         self.n_dict, self.lr, self.beta1, self.beta2,
-                         self.eps, EPS_NORM, True,
-                         w_used=self.Wc, clamp_mask=True, lr_mult=self.lr_mult)
-        ext.bias_adam(p["encoder_bias"], self.g_bias, self.bias_decay,
-                      st["mu"]["encoder_bias"], st["nu"]["encoder_bias"],
-                      step_no, self.lr, self.beta1, self.beta2, self.eps,
-                      lr_mult=self.lr_mult)
+        t = self._begin_update()
+        self._adam_matrix("encoder", self.gw, t, project=True, lr_mult=self.lr_mult,
+                          w_used=self.Wc, clamp_mask=True)
+        self._adam_vector("encoder_bias", self.g_bias, t, decay=self.bias_decay, lr_mult=self.lr_mult)
 
 
 class HipThresholdStep(HipSAEStep):
@@ -625,84 +606,52 @@ class HipThresholdStep(HipSAEStep):
     Weight grads + renorm-projected Adam are the tied-SAE kernels.
     """
 
+    staging = "t"  # the gate epilogue lives only in the transpose-in-staging kernels
+
     def __init__(self, ensemble, ext):
         super().__init__(ensemble, ext, tied=True)
 
-    def _alloc(self, B: int):
-        super()._alloc(B)
-        M, n, d = self.n_models, self.n_dict, self.d_act
-        dev = self.ens.params["encoder"].device
-        self.u = torch.empty(M, B, n, device=dev)
-        self.g_gain = torch.zeros(M, n, device=dev)
-        self.g_scale = torch.zeros(M, n, device=dev)
-        self.dummy_bias = torch.zeros(M, n, device=dev)
-        self.zero_decay = torch.zeros_like(self.bias_decay)
-        # the gate epilogue lives only in the transpose-in-staging kernels
-        self.kc["staging"] = "t"
+    def _alloc_workspaces(self, B: int):
+        super()._alloc_workspaces(B)
+        M, n = self.n_models, self.n_dict
+        self.u = self._empty(M, B, n)
+        self.g_gain = self._zeros(M, n)
+        self.g_scale = self._zeros(M, n)
+        self.dummy_bias = self._zeros(M, n)
 
-    def grads_phase(self, x: torch.Tensor, on_grads=None):
-        ens, ext = self.ens, self.ext
-        B = x.shape[0]
-        if self._B != B:
-            self._alloc(B)
-        x = x.contiguous()
-        p = ens.params
+    def _grads(self, x, B, on_grads):
+        ext, bk, prio = self.ext, self.bk, self.prio
+        p = self.ens.params
         enc = p["encoder"]
         a = p["activation_scale"]
-        gain = p["activation_gain"]
-        bk, prio = self.kc["bk"], self.kc["prio"]
-        bk_gw = self.kc["bk_grad_w"] or bk
 
         self.loss_parts.zero_()
         self.g_gain.zero_()
         self.g_scale.zero_()
 
         ext.row_norms(enc, self.norms, self.inv_norms, EPS_NORM)
-        ext.enc_fwd(x, enc, self.dummy_bias, self.inv_norms, self.c,
-                    self.loss_parts, self.fired, 2, bk, prio,
-                    act_scale=a, act_gain=gain, u_out=self.u)
-        ext.dec_fwd(self.c, enc, self.inv_norms, x, self.r, self.loss_parts,
-                    self.kc["bk_dec"] or bk, prio)
+        ext.enc_fwd(x, enc, self.dummy_bias, self.inv_norms, self.c, self.loss_parts, self.fired, 2,
+                    bk, prio, self.bn_enc, act_scale=a, act_gain=p["activation_gain"], u_out=self.u)
+        ext.dec_fwd(self.c, enc, self.inv_norms, x, self.r, self.loss_parts, self.bk_dec, prio, self.bn)
         ext.gc_thresh(self.r, enc, self.inv_norms, self.c, self.u, a,
                       self.l1_alpha, self.gpre, self.g_gain, self.g_scale, bk, prio)
-
-        gscale = 2.0 / (B * self.d_act)
-        ext.grad_w(self.c, self.r, self.gw, gscale, 0.0, bk_gw, prio)
-        ext.grad_w(self.gpre, x, self.gw, 1.0, 1.0, bk_gw, prio)
-        if on_grads is not None:
-            on_grads([self.gw, self.g_gain, self.g_scale])
-        return B
+        self._weight_grads(x, B)
+        _announce(on_grads, self.gw, self.g_gain, self.g_scale)
 
     def update_phase(self, B: int):
-        ens, ext = self.ens, self.ext
-        st = ens.optim_states
-        st["step"] += 1.0
-        step_no = st["step"]
-        p = ens.params
-        zero_decay = self.zero_decay
-        ext.project_adam(p["encoder"], self.gw, self.norms,
-                         st["mu"]["encoder"], st["nu"]["encoder"], step_no,
-                         self.n_dict, self.lr, self.beta1, self.beta2,
-                         self.eps, EPS_NORM, True, lr_mult=self.lr_mult)
-        ext.bias_adam(p["activation_scale"], self.g_scale, zero_decay,
-                      st["mu"]["activation_scale"], st["nu"]["activation_scale"],
-                      step_no, self.lr, self.beta1, self.beta2, self.eps,
-                      lr_mult=self.lr_mult)
-        ext.bias_adam(p["activation_gain"], self.g_gain, zero_decay,
-                      st["mu"]["activation_gain"], st["nu"]["activation_gain"],
-                      step_no, self.lr, self.beta1, self.beta2, self.eps,
-                      lr_mult=self.lr_mult)
+        t = self._begin_update()
+        self._adam_matrix("encoder", self.gw, t, project=True, lr_mult=self.lr_mult)
+        self._adam_vector("activation_scale", self.g_scale, t, lr_mult=self.lr_mult)
+        self._adam_vector("activation_gain", self.g_gain, t, lr_mult=self.lr_mult)
 
     def _loss_data(self, B: int):
-        mse = self.loss_parts[:, 0] / (B * self.d_act)
-        l1 = self.l1_alpha * self.loss_parts[:, 1] / B
-        return {"loss": mse + l1, "l_reconstruction": mse, "l_l1": l1}
+        return self._mse_l1_loss(B, self.loss_parts[:, 1])
 
     def dp_grad_tensors(self):
         return [self.gw, self.g_gain, self.g_scale]
 
 
-class HipLISTAStep:
+class HipLISTAStep(_HipStep):
     """Fused training step for FunctionalLISTADenoisingSAE (SURVEY.md K11;
     reference residual_denoising_autoencoder.py:15-122).
 
@@ -725,40 +674,22 @@ class HipLISTAStep:
     """
 
     def __init__(self, ensemble, ext):
-        self.ens = ensemble
-        self.ext = ext
-        p = ensemble.params
-        self.n_models, self.n_dict, self.d_act = p["decoder"].shape
-        self.n_layers = len(p["encoder_layers"])
+        super().__init__(ensemble, ext)
+        self.n_layers = len(ensemble.params["encoder_layers"])
 
-        opt = ensemble.optimizer_kwargs
-        self.lr = float(opt.get("lr", 1e-3))
-        betas = opt.get("betas", (0.9, 0.999))
-        self.beta1, self.beta2 = float(betas[0]), float(betas[1])
-        self.eps = float(opt.get("eps", 1e-8))
-        if getattr(ensemble.optimizer_func, "__name__", "adam") != "adam":
-            raise RuntimeError("fused HIP step supports adam only")
-        self.l1_alpha = ensemble.buffers["l1_alpha"].detach().reshape(self.n_models).contiguous()
-        self._B = None
-        import os as _os
+    @property
+    def codes(self):
+        return self.y[self.n_layers]
 
-        self.use_graph = _os.environ.get("SPARSE_CODING_AMD_NO_GRAPH") != "1"
-        self._graph = None
-        self._eager_steps = 0
-
-    def _alloc(self, B: int):
-        from sparse_coding_amd.ops.kconfig import kernel_config
-
-        self.kc = kernel_config()
+    def _alloc_workspaces(self, B: int):
         M, n, d, L = self.n_models, self.n_dict, self.d_act, self.n_layers
-        dev = self.ens.params["decoder"].device
-        f = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+        f = self._empty
         self.norms, self.inv_norms = f(M, n), f(M, n)
-        self.ones_mn = torch.ones(M, n, device=dev)
-        self.zeros_bd = torch.zeros(B, d, device=dev)
+        self.ones_mn = self._ones(M, n)
+        self.zeros_bd = self._zeros(B, d)
         self.scratch_lp = f(M, 2)
         self.loss_parts = f(M, 2)
-        self.fired = torch.zeros(M, n, device=dev)
+        self.fired = self._zeros(M, n)
         self.mom = [f(M) for _ in range(L)]
         # forward saves
         self.y = [f(M, B, n) for _ in range(L + 1)]
@@ -769,8 +700,8 @@ class HipLISTAStep:
         # backward workspaces
         self.g_y = f(M, B, n)
         self.g_r = f(M, B, n)
-        self.carry_a = torch.zeros(M, B, n, device=dev)
-        self.carry_b = torch.zeros(M, B, n, device=dev)
+        self.carry_a = self._zeros(M, B, n)
+        self.carry_b = self._zeros(M, B, n)
         self.sgn = f(M, B, n)
         self.g_e = f(M, B, d)
         self.gA = f(M, n, d)
@@ -778,24 +709,14 @@ class HipLISTAStep:
         self.g_theta = [f(M, n) for _ in range(L)]
         self.g_rho = [f(M) for _ in range(L)]
         self.scratch_mn = f(M, n)
-        self.zero_decay = torch.zeros(M, device=dev)
-        self._B = B
-        self._graph = None
-        self._eager_steps = 0
 
-    def grads_phase(self, x_in: torch.Tensor, on_grads=None):
-        ens, ext = self.ens, self.ext
-        M, n, d, L = self.n_models, self.n_dict, self.d_act, self.n_layers
-        B = x_in.shape[0]
-        if self._B != B:
-            self._alloc(B)
-        b = x_in.contiguous()
-        p = ens.params
+    def _grads(self, b, B, on_grads):
+        ext = self.ext
+        M, d, L = self.n_models, self.d_act, self.n_layers
+        p = self.ens.params
         A = p["decoder"]
         layers = p["encoder_layers"]
-        bk, prio = self.kc["bk"], self.kc["prio"]
-        bk_dec = self.kc["bk_dec"] or bk
-        bk_gw = self.kc["bk_grad_w"] or bk
+        bk, prio, bk_dec, bk_gw = self.bk, self.prio, self.bk_dec, self.bk_gw
 
         self.loss_parts.zero_()
         ext.row_norms(A, self.norms, self.inv_norms, EPS_NORM)
@@ -835,8 +756,7 @@ class HipLISTAStep:
                                self.x[l + 1], self.x[l], self.mom[l],
                                self.g_r, carry_out, self.g_theta[l], self.g_rho[l])
             ext.grad_w(self.g_r, self.neg_e[l], self.gW[l], -1.0, 0.0, bk_gw, prio)
-            if on_grads is not None:
-                on_grads([self.gW[l], self.g_theta[l], self.g_rho[l]])
+            _announce(on_grads, self.gW[l], self.g_theta[l], self.g_rho[l])
             ext.dec_fwd(self.g_r, layers[l]["W"], self.ones_mn, self.zeros_bd,
                         self.g_e, self.scratch_lp, bk_dec, prio)
             ext.grad_w(self.y[l], self.g_e, self.gA, -1.0, 1.0, bk_gw, prio)
@@ -849,41 +769,21 @@ class HipLISTAStep:
         # x0 = y0: remaining carry lands on g_y0
         self.g_y.add_(carry_in)
         ext.grad_w(self.g_y, b, self.gA, 1.0, 1.0, bk_gw, prio)
-        if on_grads is not None:
-            on_grads([self.gA])
-        return B
+        _announce(on_grads, self.gA)
 
     def update_phase(self, B: int):
-        ens, ext = self.ens, self.ext
-        st = ens.optim_states
-        st["step"] += 1.0
-        step_no = st["step"]
-        p = ens.params
-        ext.project_adam(p["decoder"], self.gA, self.norms,
-                         st["mu"]["decoder"], st["nu"]["decoder"], step_no,
-                         self.n_dict, self.lr, self.beta1, self.beta2,
-                         self.eps, EPS_NORM, True)
+        t = self._begin_update()
+        self._adam_matrix("decoder", self.gA, t, project=True)
         for l in range(self.n_layers):
-            ext.project_adam(p["encoder_layers"][l]["W"], self.gW[l], self.norms,
-                             st["mu"]["encoder_layers"][l]["W"],
-                             st["nu"]["encoder_layers"][l]["W"], step_no,
-                             self.n_dict, self.lr, self.beta1, self.beta2,
-                             self.eps, EPS_NORM, False)
-            ext.bias_adam(p["encoder_layers"][l]["theta"], self.g_theta[l],
-                          self.zero_decay,
-                          st["mu"]["encoder_layers"][l]["theta"],
-                          st["nu"]["encoder_layers"][l]["theta"],
-                          step_no, self.lr, self.beta1, self.beta2, self.eps)
+            self._adam_matrix(("encoder_layers", l, "W"), self.gW[l], t, project=False)
+            self._adam_vector(("encoder_layers", l, "theta"), self.g_theta[l], t)
             # clamp gate on rho (identical on every DP rank)
-            rho = p["encoder_layers"][l]["rho"].reshape(self.n_models)
+            rho = self.ens.params["encoder_layers"][l]["rho"].reshape(self.n_models)
             self.g_rho[l].mul_(((rho > 0.0) & (rho < 1.0)).float())
-            self._apply_rho_adam(l, step_no)
+            self._apply_rho_adam(l, t)
 
     def _apply_rho_adam(self, l, step_no):
-        st = self.ens.optim_states
-        rho = self.ens.params["encoder_layers"][l]["rho"]
-        mu = st["mu"]["encoder_layers"][l]["rho"]
-        nu = st["nu"]["encoder_layers"][l]["rho"]
+        rho, mu, nu = self._param_state(("encoder_layers", l, "rho"))
         g = self.g_rho[l].reshape(rho.shape)
         t = step_no.reshape(rho.shape)
         mu.mul_(self.beta1).add_(g, alpha=1 - self.beta1)
@@ -893,46 +793,14 @@ class HipLISTAStep:
         rho.sub_(self.lr * (mu / bc1) / ((nu / bc2).sqrt() + self.eps))
 
     def _loss_data(self, B: int):
-        mse = self.loss_parts[:, 0] / (B * self.d_act)
-        self.ext.colsum(self.y[self.n_layers], self.scratch_mn, absval=True)
-        l1 = self.l1_alpha * self.scratch_mn.sum(dim=1) / B
-        return {"loss": mse + l1, "l_reconstruction": mse, "l_l1": l1}
-
-    def _capture(self, x: torch.Tensor) -> None:
-        try:
-            self.x_static = x.clone()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                B = self.grads_phase(self.x_static)
-                self.update_phase(B)
-            self._graph = g
-        except Exception as e:  # noqa: BLE001 - graphs are an optimization only
-            print(f"[hip_step] hipGraph capture failed ({e}); staying eager")
-            self.use_graph = False
-            self._graph = None
-
-    def step(self, minibatches: torch.Tensor, expand_dims: bool = True):
-        if not expand_dims:
-            raise NotImplementedError("per-model batches not supported by the HIP step")
-        B = minibatches.shape[0]
-        if self.use_graph:
-            if self._B == B and self._graph is None and self._eager_steps >= 2:
-                self._capture(minibatches.contiguous())
-            if self._graph is not None:
-                self.x_static.copy_(minibatches)
-                self._graph.replay()
-                return self._loss_data(B), {"c": self.y[self.n_layers]}
-        B = self.grads_phase(minibatches)
-        self.update_phase(B)
-        self._eager_steps += 1
-        return self._loss_data(B), {"c": self.y[self.n_layers]}
+        self.ext.colsum(self.codes, self.scratch_mn, absval=True)
+        return self._mse_l1_loss(B, self.scratch_mn.sum(dim=1))
 
     def dp_grad_tensors(self):
         return [self.gA] + self.gW + self.g_theta + self.g_rho
 
 
-class HipResidualDenoisingStep:
+class HipResidualDenoisingStep(_HipStep):
     """Fused step for FunctionalResidualDenoisingSAE
     (residual_denoising_autoencoder.py:125-201): x0 = b A_hat^T, then
     L residual blocks x' = relu(x + theta_l) W_l^T + x (W_l is [n, n]),
@@ -940,35 +808,22 @@ class HipResidualDenoisingStep:
     all GEMMs (including the [n,n] layer products) run on the MFMA kernels.
     """
 
+    # runs eagerly: turning capture on is a performance change, to be measured on its own
+    captures_graph = False
+
     def __init__(self, ensemble, ext):
-        self.ens = ensemble
-        self.ext = ext
-        p = ensemble.params
-        self.n_models, self.n_dict, self.d_act = p["decoder"].shape
-        self.n_layers = len(p["encoder_layers"])
-        opt = ensemble.optimizer_kwargs
-        self.lr = float(opt.get("lr", 1e-3))
-        betas = opt.get("betas", (0.9, 0.999))
-        self.beta1, self.beta2 = float(betas[0]), float(betas[1])
-        self.eps = float(opt.get("eps", 1e-8))
-        if getattr(ensemble.optimizer_func, "__name__", "adam") != "adam":
-            raise RuntimeError("fused HIP step supports adam only")
-        self.l1_alpha = ensemble.buffers["l1_alpha"].detach().reshape(self.n_models).contiguous()
-        self._B = None
+        super().__init__(ensemble, ext)
+        self.n_layers = len(ensemble.params["encoder_layers"])
 
-    def _alloc(self, B: int):
-        from sparse_coding_amd.ops.kconfig import kernel_config
-
-        self.kc = kernel_config()
+    def _alloc_workspaces(self, B: int):
         M, n, d, L = self.n_models, self.n_dict, self.d_act, self.n_layers
-        dev = self.ens.params["decoder"].device
-        f = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+        f = self._empty
         self.norms, self.inv_norms = f(M, n), f(M, n)
-        self.ones_mn = torch.ones(M, n, device=dev)
-        self.zeros_bn = torch.zeros(B, n, device=dev)
+        self.ones_mn = self._ones(M, n)
+        self.zeros_bn = self._zeros(B, n)
         self.scratch_lp = f(M, 2)
         self.loss_parts = f(M, 2)
-        self.fired = torch.zeros(M, n, device=dev)
+        self.fired = self._zeros(M, n)
         self.xs = [f(M, B, n) for _ in range(L + 1)]
         self.hs = [f(M, B, n) for _ in range(L)]
         self.c = f(M, B, n)
@@ -980,26 +835,16 @@ class HipResidualDenoisingStep:
         self.g_theta = [f(M, n) for _ in range(L)]
         self.g_bias = f(M, n)
         self.scratch_mn = f(M, n)
-        self.zero_decay = torch.zeros(M, device=dev)
-        self._B = B
 
-    def grads_phase(self, x_in: torch.Tensor, on_grads=None):
-        ens, ext = self.ens, self.ext
-        M, n, d, L = self.n_models, self.n_dict, self.d_act, self.n_layers
-        B = x_in.shape[0]
-        if self._B != B:
-            self._alloc(B)
-        b = x_in.contiguous()
-        p = ens.params
+    def _grads(self, b, B, on_grads):
+        ext = self.ext
+        L = self.n_layers
+        p = self.ens.params
         A = p["decoder"]
         layers = p["encoder_layers"]
-        bias = p["encoder_bias"]
-        bk, prio = self.kc["bk"], self.kc["prio"]
-        bk_dec = self.kc["bk_dec"] or bk
-        bk_gw = self.kc["bk_grad_w"] or bk
+        bk, prio, bk_dec, bk_gw = self.bk, self.prio, self.bk_dec, self.bk_gw
 
         self.loss_parts.zero_()
-        self.g_bias.zero_()
         ext.row_norms(A, self.norms, self.inv_norms, EPS_NORM)
 
         # forward
@@ -1013,7 +858,7 @@ class HipResidualDenoisingStep:
             ext.enc_fwd(self.hs[l], W_l, self.ones_mn, None, self.xs[l + 1],
                         self.scratch_lp, self.fired, 1, bk, prio)
             self.xs[l + 1].add_(self.xs[l])
-        torch.add(self.xs[L], bias.unsqueeze(1), out=self.c)
+        torch.add(self.xs[L], p["encoder_bias"].unsqueeze(1), out=self.c)
         self.c.clamp_(min=0.0)
 
         ext.dec_fwd(self.c, A, self.inv_norms, b, self.rr, self.loss_parts, bk_dec, prio)
@@ -1025,18 +870,16 @@ class HipResidualDenoisingStep:
 
         # backward: g_c via k_gc (relu mask + l1 term + bias colsum, K=d)
         ext.gc(self.rr, A, self.inv_norms, self.c, self.l1_alpha,
-               self.g_x, self.g_bias, bk, prio)
-        gscale = 2.0 / (B * d)
+               self.g_x, self.g_bias, bk, prio, accumulate=False)
+        gscale = 2.0 / (B * self.d_act)
         ext.grad_w(self.c, self.rr, self.gA, gscale, 0.0, bk_gw, prio)
 
         for l in range(L - 1, -1, -1):
-            W_l, theta = layers[l]["W"], layers[l]["theta"]
             # g_W_l = g_x'^T h
             ext.grad_w(self.g_x, self.hs[l], self.gW[l], 1.0, 0.0, bk_gw, prio)
-            if on_grads is not None:
-                on_grads([self.gW[l]])
+            _announce(on_grads, self.gW[l])
             # g_h = g_x' @ W_l  ([M,B,n] x [M,n,n])
-            ext.dec_fwd(self.g_x, W_l, self.ones_mn, self.zeros_bn, self.g_h,
+            ext.dec_fwd(self.g_x, layers[l]["W"], self.ones_mn, self.zeros_bn, self.g_h,
                         self.scratch_lp, bk_dec, prio)
             # relu(x + theta) backward
             self.g_h.mul_((self.hs[l] > 0).float())
@@ -1045,95 +888,54 @@ class HipResidualDenoisingStep:
             # = 5% of the step); the coalesced-row kernel streams the same
             # bytes at HBM rate
             ext.colsum(self.g_h, self.g_theta[l])
-            if on_grads is not None:
-                on_grads([self.g_theta[l]])
+            _announce(on_grads, self.g_theta[l])
             self.g_x.add_(self.g_h)  # residual skip + through-layer paths
 
         # x0 = b A_hat^T
         ext.grad_w(self.g_x, b, self.gA, 1.0, 1.0, bk_gw, prio)
-        if on_grads is not None:
-            on_grads([self.gA, self.g_bias])
-        return B
+        _announce(on_grads, self.gA, self.g_bias)
 
     def update_phase(self, B: int):
-        ens, ext = self.ens, self.ext
-        st = ens.optim_states
-        st["step"] += 1.0
-        step_no = st["step"]
-        p = ens.params
-        ext.project_adam(p["decoder"], self.gA, self.norms,
-                         st["mu"]["decoder"], st["nu"]["decoder"], step_no,
-                         self.n_dict, self.lr, self.beta1, self.beta2,
-                         self.eps, EPS_NORM, True)
+        t = self._begin_update()
+        self._adam_matrix("decoder", self.gA, t, project=True)
         for l in range(self.n_layers):
-            ext.project_adam(p["encoder_layers"][l]["W"], self.gW[l], self.norms,
-                             st["mu"]["encoder_layers"][l]["W"],
-                             st["nu"]["encoder_layers"][l]["W"], step_no,
-                             self.n_dict, self.lr, self.beta1, self.beta2,
-                             self.eps, EPS_NORM, False)
-            ext.bias_adam(p["encoder_layers"][l]["theta"], self.g_theta[l],
-                          self.zero_decay,
-                          st["mu"]["encoder_layers"][l]["theta"],
-                          st["nu"]["encoder_layers"][l]["theta"],
-                          step_no, self.lr, self.beta1, self.beta2, self.eps)
-        ext.bias_adam(p["encoder_bias"], self.g_bias, self.zero_decay,
-                      st["mu"]["encoder_bias"], st["nu"]["encoder_bias"],
-                      step_no, self.lr, self.beta1, self.beta2, self.eps)
+            self._adam_matrix(("encoder_layers", l, "W"), self.gW[l], t, project=False)
+            self._adam_vector(("encoder_layers", l, "theta"), self.g_theta[l], t)
+        self._adam_vector("encoder_bias", self.g_bias, t)
 
     def _loss_data(self, B: int):
-        mse = self.loss_parts[:, 0] / (B * self.d_act)
-        l1 = self.l1_alpha * self._l1_sum / B
-        return {"loss": mse + l1, "l_reconstruction": mse, "l_l1": l1}
-
-    def step(self, minibatches: torch.Tensor, expand_dims: bool = True):
-        if not expand_dims:
-            raise NotImplementedError
-        B = self.grads_phase(minibatches)
-        self.update_phase(B)
-        return self._loss_data(B), {"c": self.c}
+        return self._mse_l1_loss(B, self._l1_sum)
 
     def dp_grad_tensors(self):
         return [self.gA, self.g_bias] + self.gW + self.g_theta
 
 
-class HipSemilinearStep:
+class HipSemilinearStep(_HipStep):
     """Fused step for SemiLinearSAE (semilinear_autoencoder.py:14-83): a
     2-layer relu MLP encoder + normalized linear decoder.  The top-layer
     backward IS k_gc (relu mask + l1 + bias column sums); the hidden layer
     is one more GEMM pair.
     """
 
+    # runs eagerly: turning capture on is a performance change, to be measured on its own
+    captures_graph = False
+
     def __init__(self, ensemble, ext):
-        self.ens = ensemble
-        self.ext = ext
-        p = ensemble.params
-        self.n_models, self.n_dict, self.d_act = p["decoder"].shape
-        self.hidden = p["encoder_layers"][0]["weight"].shape[1]  # [M, h, d] -> h
-        assert len(p["encoder_layers"]) == 2
-        opt = ensemble.optimizer_kwargs
-        self.lr = float(opt.get("lr", 1e-3))
-        betas = opt.get("betas", (0.9, 0.999))
-        self.beta1, self.beta2 = float(betas[0]), float(betas[1])
-        self.eps = float(opt.get("eps", 1e-8))
-        if getattr(ensemble.optimizer_func, "__name__", "adam") != "adam":
-            raise RuntimeError("fused HIP step supports adam only")
-        self.l1_alpha = ensemble.buffers["l1_alpha"].detach().reshape(self.n_models).contiguous()
-        self._B = None
+        super().__init__(ensemble, ext)
+        layers = ensemble.params["encoder_layers"]
+        assert len(layers) == 2
+        self.hidden = layers[0]["weight"].shape[1]  # [M, h, d] -> h
 
-    def _alloc(self, B: int):
-        from sparse_coding_amd.ops.kconfig import kernel_config
-
-        self.kc = kernel_config()
+    def _alloc_workspaces(self, B: int):
         M, n, d, h = self.n_models, self.n_dict, self.d_act, self.hidden
-        dev = self.ens.params["decoder"].device
-        f = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+        f = self._empty
         self.norms, self.inv_norms = f(M, n), f(M, n)
-        self.ones_mh = torch.ones(M, h, device=dev)
-        self.zeros_bh = torch.zeros(B, h, device=dev)
+        self.ones_mh = self._ones(M, h)
+        self.zeros_bh = self._zeros(B, h)
         self.scratch_lp = f(M, 2)
         self.loss_parts = f(M, 2)
-        self.fired = torch.zeros(M, n, device=dev)
-        self.fired_h = torch.zeros(M, h, device=dev)
+        self.fired = self._zeros(M, n)
+        self.fired_h = self._zeros(M, h)
         self.h1 = f(M, B, h)
         self.c = f(M, B, n)
         self.rr = f(M, B, d)
@@ -1145,24 +947,15 @@ class HipSemilinearStep:
         self.g_b2 = f(M, n)
         self.g_b1 = f(M, h)
         self.scratch_mn = f(M, n)
-        self.zero_decay = torch.zeros(M, device=dev)
-        self._B = B
 
-    def grads_phase(self, x_in: torch.Tensor, on_grads=None):
-        ens, ext = self.ens, self.ext
-        B = x_in.shape[0]
-        if self._B != B:
-            self._alloc(B)
-        b = x_in.contiguous()
-        p = ens.params
+    def _grads(self, b, B, on_grads):
+        ext = self.ext
+        p = self.ens.params
         A = p["decoder"]
         l1p, l2p = p["encoder_layers"]
-        bk, prio = self.kc["bk"], self.kc["prio"]
-        bk_dec = self.kc["bk_dec"] or bk
-        bk_gw = self.kc["bk_grad_w"] or bk
+        bk, prio, bk_dec, bk_gw = self.bk, self.prio, self.bk_dec, self.bk_gw
 
         self.loss_parts.zero_()
-        self.g_b2.zero_()
         ext.row_norms(A, self.norms, self.inv_norms, EPS_NORM)
 
         # h1 = relu(b W1^T + b1);  c = relu(h1 W2^T + b2)
@@ -1178,7 +971,7 @@ class HipSemilinearStep:
 
         # backward
         ext.gc(self.rr, A, self.inv_norms, self.c, self.l1_alpha,
-               self.g_c, self.g_b2, bk, prio)
+               self.g_c, self.g_b2, bk, prio, accumulate=False)
         gscale = 2.0 / (B * self.d_act)
         ext.grad_w(self.c, self.rr, self.gA, gscale, 0.0, bk_gw, prio)
         ext.grad_w(self.g_c, self.h1, self.gW2, 1.0, 0.0, bk_gw, prio)
@@ -1190,94 +983,48 @@ class HipSemilinearStep:
         # rocprof r02_semilinear_kernel_stats)
         ext.colsum(self.g_h, self.g_b1)
         ext.grad_w(self.g_h, b, self.gW1, 1.0, 0.0, bk_gw, prio)
-        if on_grads is not None:
-            on_grads([self.gA, self.gW2, self.gW1, self.g_b2, self.g_b1])
-        return B
+        _announce(on_grads, self.gA, self.gW2, self.gW1, self.g_b2, self.g_b1)
 
     def update_phase(self, B: int):
-        ens, ext = self.ens, self.ext
-        st = ens.optim_states
-        st["step"] += 1.0
-        step_no = st["step"]
-        p = ens.params
-        ext.project_adam(p["decoder"], self.gA, self.norms,
-                         st["mu"]["decoder"], st["nu"]["decoder"], step_no,
-                         self.n_dict, self.lr, self.beta1, self.beta2,
-                         self.eps, EPS_NORM, True)
+        t = self._begin_update()
+        self._adam_matrix("decoder", self.gA, t, project=True)
         for li, (gW, gb) in enumerate(((self.gW1, self.g_b1), (self.gW2, self.g_b2))):
-            lay = p["encoder_layers"][li]
-            ext.project_adam(lay["weight"], gW, self.norms,
-                             st["mu"]["encoder_layers"][li]["weight"],
-                             st["nu"]["encoder_layers"][li]["weight"], step_no,
-                             gW.shape[1], self.lr, self.beta1, self.beta2,
-                             self.eps, EPS_NORM, False)
-            ext.bias_adam(lay["bias"], gb, self.zero_decay,
-                          st["mu"]["encoder_layers"][li]["bias"],
-                          st["nu"]["encoder_layers"][li]["bias"],
-                          step_no, self.lr, self.beta1, self.beta2, self.eps)
+            self._adam_matrix(("encoder_layers", li, "weight"), gW, t, project=False,
+                              n_per_model=gW.shape[1])
+            self._adam_vector(("encoder_layers", li, "bias"), gb, t)
 
     def _loss_data(self, B: int):
-        mse = self.loss_parts[:, 0] / (B * self.d_act)
-        l1 = self.l1_alpha * self._l1_sum / B
-        return {"loss": mse + l1, "l_reconstruction": mse, "l_l1": l1}
-
-    def step(self, minibatches: torch.Tensor, expand_dims: bool = True):
-        if not expand_dims:
-            raise NotImplementedError
-        B = self.grads_phase(minibatches)
-        self.update_phase(B)
-        return self._loss_data(B), {"c": self.c}
+        return self._mse_l1_loss(B, self._l1_sum)
 
     def dp_grad_tensors(self):
         return [self.gA, self.gW1, self.gW2, self.g_b1, self.g_b2]
 
 
-class HipTopKStep:
+class HipTopKStep(_HipStep):
     """Fused TopK-encoder training step.
 
     Same GEMM pipeline as the tied SAE but: raw-score encoder (no bias/relu),
     per-row top-k selection + scatter + relu between encode and decode, no L1
     term, and the dictionary normalization has NO eps clamp
     (reference topk_encoder.py:31).  The per-model k lives in
-    buffers["sparsity"]; selection runs as one torch.topk per model.
+    buffers["sparsity"]; selection runs in one kernel (k_topk_select).
     """
 
     EPS = 1e-30  # un-clamped normalization (reference divides by the raw norm)
+    dict_key = "dict"
 
     def __init__(self, ensemble, ext):
-        self.ens = ensemble
-        self.ext = ext
-        p = ensemble.params
-        self.n_models, self.n_dict, self.d_act = p["dict"].shape
-        dev = p["dict"].device
+        super().__init__(ensemble, ext)
+        dev = self._dev
         self.ks = [int(k) for k in ensemble.buffers["sparsity"].reshape(-1).tolist()]
         self.ks_i32 = torch.tensor(self.ks, device=dev, dtype=torch.int32)
         self.zero_l1 = torch.zeros(self.n_models, device=dev)
         self.dummy_bias = torch.zeros(self.n_models, self.n_dict, device=dev)
         self.lr_mult = torch.ones(self.n_models, self.n_dict, device=dev)
 
-        opt = ensemble.optimizer_kwargs
-        self.lr = float(opt.get("lr", 1e-3))
-        betas = opt.get("betas", (0.9, 0.999))
-        self.beta1, self.beta2 = float(betas[0]), float(betas[1])
-        self.eps = float(opt.get("eps", 1e-8))
-        name = getattr(ensemble.optimizer_func, "__name__", "adam")
-        if name != "adam":
-            raise RuntimeError(f"fused HIP step supports adam only, got {name}")
-        self._B = None
-        import os as _os
-
-        self.use_graph = _os.environ.get("SPARSE_CODING_AMD_NO_GRAPH") != "1"
-        self._graph = None
-        self._eager_steps = 0
-
-    def _alloc(self, B):
-        from sparse_coding_amd.ops.kconfig import kernel_config
-
-        self.kc = kernel_config()
+    def _alloc_workspaces(self, B: int):
         M, n, d = self.n_models, self.n_dict, self.d_act
-        dev = self.ens.params["dict"].device
-        f = lambda *shape: torch.empty(shape, device=dev, dtype=torch.float32)
+        f = self._empty
         self.scores = f(M, B, n)
         self.c = f(M, B, n)
         self.gpre = f(M, B, n)
@@ -1285,28 +1032,15 @@ class HipTopKStep:
         self.norms = f(M, n)
         self.inv_norms = f(M, n)
         self.loss_parts = f(M, 2)
-        self.fired = torch.zeros(M, n, device=dev)
+        self.fired = self._zeros(M, n)
         self.g_bias_scratch = f(M, n)
         self.gw = f(M, n, d)
-        self._B = B
-        self._graph = None
-        self._eager_steps = 0
 
-    def grads_phase(self, x):
-        ens, ext = self.ens, self.ext
-        B = x.shape[0]
-        if self._B != B:
-            self._alloc(B)
-        x = x.contiguous()
-        W = ens.params["dict"]
+    def _grads(self, x, B, on_grads):
+        ext, bk, prio, bk_gw = self.ext, self.bk, self.prio, self.bk_gw
+        W = self.ens.params["dict"]
 
         self.loss_parts.zero_()
-        self.g_bias_scratch.zero_()
-
-        kc = self.kc
-        bk, prio = kc["bk"], kc["prio"]
-        bk_dec = kc["bk_dec"] or bk
-        bk_gw = kc["bk_grad_w"] or bk
         ext.row_norms(W, self.norms, self.inv_norms, self.EPS)
         ext.enc_fwd(x, W, self.dummy_bias, self.inv_norms,
                     self.scores, self.loss_parts, self.fired, 1, bk, prio)
@@ -1314,57 +1048,21 @@ class HipTopKStep:
         # (k_topk_select) — replaces the torch.topk/scatter chain
         ext.topk_select(self.scores, self.c, self.fired, self.ks_i32)
 
-        ext.dec_fwd(self.c, W, self.inv_norms, x, self.r, self.loss_parts, bk_dec, prio)
+        ext.dec_fwd(self.c, W, self.inv_norms, x, self.r, self.loss_parts, self.bk_dec, prio)
         ext.gc(self.r, W, self.inv_norms, self.c, self.zero_l1,
-               self.gpre, self.g_bias_scratch, bk, prio)
+               self.gpre, self.g_bias_scratch, bk, prio, accumulate=False)
         gscale = 2.0 / (B * self.d_act)
         ext.grad_w(self.c, self.r, self.gw, gscale, 0.0, bk_gw, prio)
         ext.grad_w(self.gpre, x, self.gw, 1.0, 1.0, bk_gw, prio)
-        return B
+        _announce(on_grads, self.gw)
 
-    def update_phase(self, B):
-        ens, ext = self.ens, self.ext
-        st = ens.optim_states
-        st["step"] += 1.0
-        ext.project_adam(ens.params["dict"], self.gw, self.norms,
-                         st["mu"]["dict"], st["nu"]["dict"], st["step"],
-                         self.n_dict, self.lr, self.beta1, self.beta2,
-                         self.eps, self.EPS, True, lr_mult=self.lr_mult)
+    def update_phase(self, B: int):
+        t = self._begin_update()
+        self._adam_matrix("dict", self.gw, t, project=True, lr_mult=self.lr_mult, eps_norm=self.EPS)
 
-    def _loss_data(self, B):
+    def _loss_data(self, B: int):
         mse = self.loss_parts[:, 0] / (B * self.d_act)
         return {"loss": mse}
-
-    def _capture(self, x):
-        try:
-            self.x_static = x.clone()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                B = self.grads_phase(self.x_static)
-                self.update_phase(B)
-            self._graph = g
-        except Exception as e:  # noqa: BLE001 - graphs are an optimization only
-            print(f"[hip_step] hipGraph capture failed ({e}); staying eager")
-            self.use_graph = False
-            self._graph = None
-
-    def step(self, minibatches, expand_dims=True):
-        if not expand_dims:
-            # per-model batches not needed: TopK stacks fine on this path
-            raise NotImplementedError
-        B = minibatches.shape[0]
-        if self.use_graph:
-            if self._B == B and self._graph is None and self._eager_steps >= 2:
-                self._capture(minibatches.contiguous())
-            if self._graph is not None:
-                self.x_static.copy_(minibatches)
-                self._graph.replay()
-                return self._loss_data(B), {"c": self.c}
-        B = self.grads_phase(minibatches)
-        self.update_phase(B)
-        self._eager_steps += 1
-        return self._loss_data(B), {"c": self.c}
 
     def dp_grad_tensors(self):
         return [self.gw]

@@ -18,6 +18,25 @@ static inline hipStream_t cur_stream() {
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
+// Tile dispatch for the GEMM launchers, stated once.  The kernels are
+// instantiated as <TBK, MINW[, TBN]>: <16, 6> and <32, 4> are the two depths
+// of the 128x128 tile, <16, 4, 256> is the 128x256 tile.  LAUNCH_TILE picks by
+// tile depth alone (kernels without a 256-wide variant); LAUNCH_TILE_BN takes
+// the 256-wide one when bn == 256.  Each launcher states its grid and its
+// argument list once.
+#define LAUNCH_AS(kern, grid, ...) \
+  hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), 0, cur_stream(), __VA_ARGS__)
+#define LAUNCH_TILE(kern, bk, grid, ...)                          \
+  do {                                                            \
+    if ((bk) == 16) LAUNCH_AS((kern<16, 6>), grid, __VA_ARGS__);  \
+    else LAUNCH_AS((kern<32, 4>), grid, __VA_ARGS__);             \
+  } while (0)
+#define LAUNCH_TILE_BN(kern, bn, bk, grid, ...)                           \
+  do {                                                                    \
+    if ((bn) == 256) LAUNCH_AS((kern<16, 4, 256>), grid, __VA_ARGS__);    \
+    else LAUNCH_TILE(kern, bk, grid, __VA_ARGS__);                        \
+  } while (0)
+
 void row_norms(torch::Tensor W, torch::Tensor norms, torch::Tensor inv_norms, double eps) {
   CHECK_IN(W); CHECK_IN(norms); CHECK_IN(inv_norms);
   long rows = W.numel() / W.size(-1);
@@ -92,27 +111,12 @@ void enc_fwd(torch::Tensor x, torch::Tensor Wenc, torch::Tensor bias,
     }
   }
   dim3 grid(cdiv(n, bn == 256 ? 256 : BN), cdiv(B, BM), M);
-  if (bn == 256)
-    hipLaunchKernelGGL((k_enc_fwd_t<16, 4, 256>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       x.data_ptr<float>(), Wenc.data_ptr<float>(),
-                       bias.data_ptr<float>(), inv, c_out.data_ptr<float>(),
-                       loss_parts.data_ptr<float>(), fired.data_ptr<float>(),
-                       B, d, n, (int)mode, prio ? 1 : 0, a_p, gn_p, u_p, ds_p, x_mstride,
-                       yin_p, xp_p, xo_p, mom_p);
-  else if (bk == 16)
-    hipLaunchKernelGGL((k_enc_fwd_t<16, 6>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       x.data_ptr<float>(), Wenc.data_ptr<float>(),
-                       bias.data_ptr<float>(), inv, c_out.data_ptr<float>(),
-                       loss_parts.data_ptr<float>(), fired.data_ptr<float>(),
-                       B, d, n, (int)mode, prio ? 1 : 0, a_p, gn_p, u_p, ds_p, x_mstride,
-                       yin_p, xp_p, xo_p, mom_p);
-  else
-    hipLaunchKernelGGL((k_enc_fwd_t<32, 4>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       x.data_ptr<float>(), Wenc.data_ptr<float>(),
-                       bias.data_ptr<float>(), inv, c_out.data_ptr<float>(),
-                       loss_parts.data_ptr<float>(), fired.data_ptr<float>(),
-                       B, d, n, (int)mode, prio ? 1 : 0, a_p, gn_p, u_p, ds_p, x_mstride,
-                       yin_p, xp_p, xo_p, mom_p);
+  LAUNCH_TILE_BN(k_enc_fwd_t, bn, bk, grid,
+                 x.data_ptr<float>(), Wenc.data_ptr<float>(),
+                 bias.data_ptr<float>(), inv, c_out.data_ptr<float>(),
+                 loss_parts.data_ptr<float>(), fired.data_ptr<float>(),
+                 B, d, n, (int)mode, prio ? 1 : 0, a_p, gn_p, u_p, ds_p, x_mstride,
+                 yin_p, xp_p, xo_p, mom_p);
 }
 
 void dec_fwd(torch::Tensor c, torch::Tensor Wdec, torch::Tensor inv_norms,
@@ -128,24 +132,11 @@ void dec_fwd(torch::Tensor c, torch::Tensor Wdec, torch::Tensor inv_norms,
   }
   int B = x.size(x.dim() - 2);
   dim3 grid(cdiv(d, bn == 256 ? 256 : BN), cdiv(B, BM), M);
-  if (bn == 256)
-    hipLaunchKernelGGL((k_dec_fwd_t<16, 4, 256>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       c.data_ptr<float>(), Wdec.data_ptr<float>(),
-                       inv_norms.data_ptr<float>(), x.data_ptr<float>(),
-                       r_out.data_ptr<float>(), loss_parts.data_ptr<float>(),
-                       B, d, n, prio ? 1 : 0, x_mstride);
-  else if (bk == 16)
-    hipLaunchKernelGGL((k_dec_fwd_t<16, 6>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       c.data_ptr<float>(), Wdec.data_ptr<float>(),
-                       inv_norms.data_ptr<float>(), x.data_ptr<float>(),
-                       r_out.data_ptr<float>(), loss_parts.data_ptr<float>(),
-                       B, d, n, prio ? 1 : 0, x_mstride);
-  else
-    hipLaunchKernelGGL((k_dec_fwd_t<32, 4>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       c.data_ptr<float>(), Wdec.data_ptr<float>(),
-                       inv_norms.data_ptr<float>(), x.data_ptr<float>(),
-                       r_out.data_ptr<float>(), loss_parts.data_ptr<float>(),
-                       B, d, n, prio ? 1 : 0, x_mstride);
+  LAUNCH_TILE_BN(k_dec_fwd_t, bn, bk, grid,
+                 c.data_ptr<float>(), Wdec.data_ptr<float>(),
+                 inv_norms.data_ptr<float>(), x.data_ptr<float>(),
+                 r_out.data_ptr<float>(), loss_parts.data_ptr<float>(),
+                 B, d, n, prio ? 1 : 0, x_mstride);
 }
 
 void gc(torch::Tensor r, torch::Tensor Wdec, torch::Tensor inv_norms,
@@ -168,24 +159,11 @@ void gc(torch::Tensor r, torch::Tensor Wdec, torch::Tensor inv_norms,
     part = torch::empty({M, nrg, n}, r.options());
     part_p = part.data_ptr<float>();
   }
-  if (bn == 256)
-    hipLaunchKernelGGL((k_gc_t<16, 4, 256>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       r.data_ptr<float>(), Wdec.data_ptr<float>(),
-                       inv_norms.data_ptr<float>(), c.data_ptr<float>(),
-                       l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
-                       part_p, B, d, n, prio ? 1 : 0, (int)gc_mode);
-  else if (bk == 16)
-    hipLaunchKernelGGL((k_gc_t<16, 6>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       r.data_ptr<float>(), Wdec.data_ptr<float>(),
-                       inv_norms.data_ptr<float>(), c.data_ptr<float>(),
-                       l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
-                       part_p, B, d, n, prio ? 1 : 0, (int)gc_mode);
-  else
-    hipLaunchKernelGGL((k_gc_t<32, 4>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       r.data_ptr<float>(), Wdec.data_ptr<float>(),
-                       inv_norms.data_ptr<float>(), c.data_ptr<float>(),
-                       l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
-                       part_p, B, d, n, prio ? 1 : 0, (int)gc_mode);
+  LAUNCH_TILE_BN(k_gc_t, bn, bk, grid,
+                 r.data_ptr<float>(), Wdec.data_ptr<float>(),
+                 inv_norms.data_ptr<float>(), c.data_ptr<float>(),
+                 l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
+                 part_p, B, d, n, prio ? 1 : 0, (int)gc_mode);
   if (gc_mode == 0) {
     long total = (long)M * n;
     hipLaunchKernelGGL(k_colsum_groups, dim3(cdiv(total, WAVE)), dim3(256), 0, cur_stream(),
@@ -204,22 +182,13 @@ void gc_thresh(torch::Tensor r, torch::Tensor Wdec, torch::Tensor inv_norms,
   int M = Wdec.size(0), n = Wdec.size(1), d = Wdec.size(2);
   int B = r.size(1);
   dim3 grid(cdiv(n, BN), cdiv(B, BM), M);
-  if (bk == 16)
-    hipLaunchKernelGGL((k_gc_thresh_t<16, 6>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       r.data_ptr<float>(), Wdec.data_ptr<float>(),
-                       inv_norms.data_ptr<float>(), c.data_ptr<float>(),
-                       u.data_ptr<float>(), act_scale.data_ptr<float>(),
-                       l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
-                       g_gain.data_ptr<float>(), g_scale.data_ptr<float>(),
-                       B, d, n, prio ? 1 : 0);
-  else
-    hipLaunchKernelGGL((k_gc_thresh_t<32, 4>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       r.data_ptr<float>(), Wdec.data_ptr<float>(),
-                       inv_norms.data_ptr<float>(), c.data_ptr<float>(),
-                       u.data_ptr<float>(), act_scale.data_ptr<float>(),
-                       l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
-                       g_gain.data_ptr<float>(), g_scale.data_ptr<float>(),
-                       B, d, n, prio ? 1 : 0);
+  LAUNCH_TILE(k_gc_thresh_t, bk, grid,
+              r.data_ptr<float>(), Wdec.data_ptr<float>(),
+              inv_norms.data_ptr<float>(), c.data_ptr<float>(),
+              u.data_ptr<float>(), act_scale.data_ptr<float>(),
+              l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
+              g_gain.data_ptr<float>(), g_scale.data_ptr<float>(),
+              B, d, n, prio ? 1 : 0);
 }
 
 // gw[m] = beta * gw[m] + alpha * P[m]^T @ Q[m]; Q may be rank-shared [B, d]
@@ -238,21 +207,10 @@ void grad_w(torch::Tensor P, torch::Tensor Q, torch::Tensor gw,
     q_stride = 0;  // shared across models
   }
   dim3 grid(cdiv(d, bn == 256 ? 256 : BN), cdiv(n, BM), M);
-  if (bn == 256)
-    hipLaunchKernelGGL((k_grad_w_t<16, 4, 256>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       P.data_ptr<float>(), p_stride, Q.data_ptr<float>(),
-                       q_stride, gw.data_ptr<float>(), (float)alpha,
-                       (float)beta, B, n, d, prio ? 1 : 0);
-  else if (bk == 16)
-    hipLaunchKernelGGL((k_grad_w_t<16, 6>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       P.data_ptr<float>(), p_stride, Q.data_ptr<float>(),
-                       q_stride, gw.data_ptr<float>(), (float)alpha,
-                       (float)beta, B, n, d, prio ? 1 : 0);
-  else
-    hipLaunchKernelGGL((k_grad_w_t<32, 4>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       P.data_ptr<float>(), p_stride, Q.data_ptr<float>(),
-                       q_stride, gw.data_ptr<float>(), (float)alpha,
-                       (float)beta, B, n, d, prio ? 1 : 0);
+  LAUNCH_TILE_BN(k_grad_w_t, bn, bk, grid,
+                 P.data_ptr<float>(), p_stride, Q.data_ptr<float>(),
+                 q_stride, gw.data_ptr<float>(), (float)alpha,
+                 (float)beta, B, n, d, prio ? 1 : 0);
 }
 
 void project_adam(torch::Tensor W, torch::Tensor gw, torch::Tensor norms,
@@ -359,18 +317,11 @@ void enc_fwd2(torch::Tensor xT, torch::Tensor WT, torch::Tensor bias,
     ds_p = dict_sizes->data_ptr<int>();
   }
   dim3 grid(cdiv(n, BN), cdiv(B, BM), M);
-  if (bk == 16)
-    hipLaunchKernelGGL((k_enc_fwd2_t<16, 6>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       xT.data_ptr<float>(), WT.data_ptr<float>(),
-                       bias.data_ptr<float>(), c_out.data_ptr<float>(),
-                       loss_parts.data_ptr<float>(), fired.data_ptr<float>(),
-                       B, d, n, (int)mode, prio ? 1 : 0, ds_p);
-  else
-    hipLaunchKernelGGL((k_enc_fwd2_t<32, 4>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       xT.data_ptr<float>(), WT.data_ptr<float>(),
-                       bias.data_ptr<float>(), c_out.data_ptr<float>(),
-                       loss_parts.data_ptr<float>(), fired.data_ptr<float>(),
-                       B, d, n, (int)mode, prio ? 1 : 0, ds_p);
+  LAUNCH_TILE(k_enc_fwd2_t, bk, grid,
+              xT.data_ptr<float>(), WT.data_ptr<float>(),
+              bias.data_ptr<float>(), c_out.data_ptr<float>(),
+              loss_parts.data_ptr<float>(), fired.data_ptr<float>(),
+              B, d, n, (int)mode, prio ? 1 : 0, ds_p);
 }
 
 void gc2(torch::Tensor rT, torch::Tensor WT, torch::Tensor c,
@@ -381,18 +332,11 @@ void gc2(torch::Tensor rT, torch::Tensor WT, torch::Tensor c,
   int M = WT.size(0), d = WT.size(1), n = WT.size(2);
   int B = rT.size(2);
   dim3 grid(cdiv(n, BN), cdiv(B, BM), M);
-  if (bk == 16)
-    hipLaunchKernelGGL((k_gc2_t<16, 6>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       rT.data_ptr<float>(), WT.data_ptr<float>(),
-                       c.data_ptr<float>(), l1_alpha.data_ptr<float>(),
-                       gpre.data_ptr<float>(), g_bias.data_ptr<float>(),
-                       B, d, n, prio ? 1 : 0, (int)gc_mode);
-  else
-    hipLaunchKernelGGL((k_gc2_t<32, 4>), grid, dim3(NTHREADS), 0, cur_stream(),
-                       rT.data_ptr<float>(), WT.data_ptr<float>(),
-                       c.data_ptr<float>(), l1_alpha.data_ptr<float>(),
-                       gpre.data_ptr<float>(), g_bias.data_ptr<float>(),
-                       B, d, n, prio ? 1 : 0, (int)gc_mode);
+  LAUNCH_TILE(k_gc2_t, bk, grid,
+              rT.data_ptr<float>(), WT.data_ptr<float>(),
+              c.data_ptr<float>(), l1_alpha.data_ptr<float>(),
+              gpre.data_ptr<float>(), g_bias.data_ptr<float>(),
+              B, d, n, prio ? 1 : 0, (int)gc_mode);
 }
 
 void topk_select(torch::Tensor scores, torch::Tensor c_out, torch::Tensor fired,

@@ -262,13 +262,13 @@ class DataParallelEnsembleTrainer:
                 # them (HipSAEStep._alloc), after which replay would write
                 # into freed tensors — identity-check the workspace object
                 # (strong ref held at capture, so the id cannot be reused)
-                if self._graph is not None and getattr(hs, "c", None) is not self._graph_ws:
+                if self._graph is not None and hs.codes is not self._graph_ws:
                     self._graph = None
                     self._graph_B = None
                 if self._graph is not None and self._graph_B == B:
                     self._x_static.copy_(local_batch)
                     self._graph.replay()
-                    return hs._loss_data(B), {"c": hs.c}
+                    return hs._loss_data(B), {"c": hs.codes}
                 if self._dp_steps >= 2 and self._graph is None and self._graph_B != B:
                     try:
                         self._x_static = local_batch.contiguous().clone()
@@ -278,9 +278,9 @@ class DataParallelEnsembleTrainer:
                             dp_step(self._x_static)
                         self._graph = g
                         self._graph_B = B
-                        self._graph_ws = hs.c
+                        self._graph_ws = hs.codes
                         self._graph.replay()  # capture does not execute
-                        return hs._loss_data(B), {"c": hs.c}
+                        return hs._loss_data(B), {"c": hs.codes}
                     except Exception as e:  # noqa: BLE001 - optimization only
                         print(f"[dp] graph capture failed ({e}); staying eager")
                         self.graph_capture = False
@@ -288,7 +288,7 @@ class DataParallelEnsembleTrainer:
 
             B = dp_step(local_batch)
             self._dp_steps += 1
-            return hs._loss_data(B), {"c": hs.c}
+            return hs._loss_data(B), {"c": hs.codes}
 
         grads, (loss_data, aux) = self.ensemble.compute_grads(local_batch)
         if self.world_size > 1:

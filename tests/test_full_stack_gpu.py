@@ -101,6 +101,71 @@ def test_dp_hip_grads_phase_split():
         assert torch.allclose(ens_a.params[k], ens_b.params[k], atol=1e-6), k
 
 
+def _clone_models(ens):
+    leaf = lambda v: v.clone() if torch.is_tensor(v) else [{kk: vv.clone() for kk, vv in lay.items()} for lay in v]
+    return [({k: leaf(v) for k, v in p.items()}, {k: v.clone() for k, v in b.items()})
+            for p, b in ens.unstack()]
+
+
+def test_topk_grads_phase_split_with_on_grads():
+    """HipTopKStep takes the trainer's on_grads callback like every other
+    fused step: the split path with the callback == step_batch, and the
+    callback is handed the one gradient tensor, gw."""
+    from sparse_coding_amd.engine.ensemble import FunctionalEnsemble
+    from sparse_coding_amd.functional.optim import adam
+    from sparse_coding_amd.models.topk import TopKEncoder
+
+    torch.manual_seed(3)
+    M, B, d, n, k = 2, 128, 64, 128, 8
+    models = [TopKEncoder.init(d, n, k) for _ in range(M)]
+    ens_a = FunctionalEnsemble(models, TopKEncoder, adam, {"lr": 1e-3}, device=DEV, backend="hip")
+    ens_b = FunctionalEnsemble(_clone_models(ens_a), TopKEncoder, adam, {"lr": 1e-3}, device=DEV, backend="hip")
+    hb = ens_b._hip_step
+    assert type(hb).__name__ == "HipTopKStep"
+    hb.use_graph = False
+
+    x = torch.randn(B, d, device=DEV)
+    for _ in range(3):
+        ens_a.step_batch(x)
+        seen = []
+        Bn = hb.grads_phase(x, on_grads=seen.extend)
+        hb.update_phase(Bn)
+        assert len(seen) == 1 and seen[0] is hb.gw
+    for key in ens_a.params:
+        assert torch.allclose(ens_a.params[key], ens_b.params[key], atol=1e-6), key
+
+
+def test_lista_codes_and_grads_phase_split():
+    """HipLISTAStep exposes its codes as `.codes` (what the data-parallel
+    trainer returns as aux["c"]), and its split path == step_batch."""
+    from sparse_coding_amd.engine.ensemble import FunctionalEnsemble
+    from sparse_coding_amd.functional.optim import adam
+    from sparse_coding_amd.models.lista import FunctionalLISTADenoisingSAE
+
+    torch.manual_seed(4)
+    M, B, d, n, L = 2, 128, 64, 128, 2
+    sig = FunctionalLISTADenoisingSAE
+    models = [sig.init(d, n, L, l1) for l1 in (1e-3, 3e-3)]
+    ens_a = FunctionalEnsemble(models, sig, adam, {"lr": 1e-3}, device=DEV, backend="hip")
+    ens_b = FunctionalEnsemble(_clone_models(ens_a), sig, adam, {"lr": 1e-3}, device=DEV, backend="hip")
+    ha, hb = ens_a._hip_step, ens_b._hip_step
+    assert type(hb).__name__ == "HipLISTAStep"
+    hb.use_graph = False
+
+    x = torch.randn(B, d, device=DEV)
+    for _ in range(3):
+        _, aux = ens_a.step_batch(x)
+        assert aux["c"] is ha.codes
+        Bn = hb.grads_phase(x, on_grads=lambda ts: None)
+        hb.update_phase(Bn)
+    assert hb.codes.shape == (M, B, n)
+    assert torch.allclose(ens_a.params["decoder"], ens_b.params["decoder"], atol=1e-6)
+    for l in range(L):
+        for key in ("W", "theta", "rho"):
+            assert torch.allclose(ens_a.params["encoder_layers"][l][key],
+                                  ens_b.params["encoder_layers"][l][key], atol=1e-6), (l, key)
+
+
 def test_gpt2small_mlpout_grid():
     """BASELINE config 3 shape: GPT-2-small MLP-out (d=768), 32-SAE
     (8 l1 x 4 ratios as 4 ensembles) — fused steps run and converge."""
