@@ -195,6 +195,13 @@ class _HipStep:
         kc = kernel_config()
         if self.staging is not None:
             kc["staging"] = self.staging
+        if kc["staging"] == "pre" and B % 4 != 0:
+            # the pre-transposed operands xT [d, B] / rT [M, d, B] have leading
+            # dimension B and are staged as float4: a ragged batch (the last
+            # one of a chunk) runs the transpose-in-staging chain instead.
+            # Resolved here, once per allocation, so the workspaces, the launch
+            # chain and a later graph capture all see the same choice.
+            kc["staging"] = "t"
         self.kc = kc
         # tile parameters, resolved once: per-kernel overrides fall back to
         # the global tile depth / width

@@ -14,6 +14,12 @@ plus a `prio` flag (s_setprio(1) on the second-dispatched wave half) and a
   staging="t"    transpose inside the GEMM staging (stride-BM+1 LDS, b32
                  writes), no separate transpose kernels
 
+"pre" needs a batch size that is a multiple of 4 (the transposed operands have
+leading dimension B and are staged as float4).  A fused step that is handed
+any other batch size, such as the ragged last batch of a chunk, resolves
+staging to "t" for that workspace allocation (engine.hip_step._HipStep._alloc),
+so every batch size trains under either setting.
+
 Defaults come from env (SC_AMD_BK / SC_AMD_PRIO / SC_AMD_STAGING) and can be
 overridden per-process via set_kernel_config() — scripts/ktune.py sweeps the
 combinations on a GPU box and the measured winner is baked into DEFAULTS.
