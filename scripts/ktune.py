@@ -1,7 +1,9 @@
 """Kernel-variant sweep for the fused SAE training step (GPU box).
 
-Times ensemble.step_batch over the (staging, bk, prio) kernel-config grid on
-the flagship bench shape and prints one JSON line per combo plus the winner.
+Times ensemble.step_batch over the (staging, bk, prio, aligned) kernel-config
+grid on the flagship bench shape and prints one JSON line per combo plus the
+winner.  `aligned` is the extension's process-wide set_aligned_tiles switch:
+guard-free GEMM kernels on tile-aligned launches (on) or the guarded ones (off).
 Run on a GPU box:  python scripts/ktune.py [--steps 30] [--batch 2048]
 
 The measured winner is then baked into sparse_coding_amd/ops/kconfig.DEFAULTS.
@@ -25,13 +27,24 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 
-def bench_combo(args, staging, bk, prio, bk_gw=None, bk_dec=None, bn=128):
-    from sparse_coding_amd.engine.ensemble import FunctionalEnsemble
-    from sparse_coding_amd.functional.optim import adam
-    from sparse_coding_amd.models.sae_signatures import FunctionalTiedSAE
+def bench_combo(args, staging, bk, prio, bk_gw=None, bk_dec=None, bn=128, aligned=True):
+    from sparse_coding_amd import ops
     from sparse_coding_amd.ops.kconfig import set_kernel_config
 
     set_kernel_config(staging=staging, bk=bk, prio=prio, bk_grad_w=bk_gw, bk_dec=bk_dec, bn=bn)
+    ext = ops.get_extension()
+    ext.set_aligned_tiles(aligned)
+    try:
+        return _time_steps(args)
+    finally:
+        ext.set_aligned_tiles(True)
+
+
+def _time_steps(args):
+    from sparse_coding_amd.engine.ensemble import FunctionalEnsemble
+    from sparse_coding_amd.functional.optim import adam
+    from sparse_coding_amd.models.sae_signatures import FunctionalTiedSAE
+
     device = "cuda:0"
     d, n_dict, M, B = args.d_model, args.d_model * args.dict_ratio, args.n_models, args.batch
     torch.manual_seed(0)
@@ -62,9 +75,9 @@ def main():
     args = p.parse_args()
 
     results = []
-    for staging, bk, prio in itertools.product(["t", "pre"], [32, 16], [False, True]):
-        ms, acts = bench_combo(args, staging, bk, prio)
-        rec = {"staging": staging, "bk": bk, "prio": prio,
+    for staging, bk, prio, aligned in itertools.product(["t", "pre"], [32, 16], [False, True], [True, False]):
+        ms, acts = bench_combo(args, staging, bk, prio, aligned=aligned)
+        rec = {"staging": staging, "bk": bk, "prio": prio, "aligned": aligned,
                "ms_per_step": round(ms, 4), "acts_per_sec": round(acts)}
         results.append(rec)
         print(json.dumps(rec), flush=True)

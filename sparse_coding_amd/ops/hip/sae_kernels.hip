@@ -12,10 +12,19 @@
 //    quadrant as 2 v_mfma_f32_32x32x2_f32 accumulators (32 AGPRs).
 //  * K-tile depth TBK is a template parameter:
 //      TBK=32, __launch_bounds__(512,4): 64-66 KB LDS, 2 blocks/CU.
-//      TBK=16, __launch_bounds__(512,6): 32-33 KB LDS, <=80 VGPRs,
+//      TBK=16, __launch_bounds__(512,6): 32-33 KB LDS, 69-70 VGPRs,
 //        3 blocks/CU — more co-resident blocks to hide barrier skew
 //        (SQ_WAIT_ANY was 25-33% of wave cycles at 2 blocks/CU).
 //    Both are compiled; the launcher picks at runtime (ops.kconfig).
+//  * ALIGNED template flag: every GEMM kernel also exists without its row,
+//    column and K-tail guards (plain float4 staging loads, unguarded epilogue
+//    accesses through one scalar base + one 32-bit lane offset).  K-loop, MFMA
+//    order and epilogue arithmetic are the guarded kernel's, so the outputs
+//    are the same bit for bit.  The launchers (sae_ops.hip) take these on
+//    tile-aligned shapes.  Without the guards the TBK=16 variants of enc, gc,
+//    gc_thresh and grad_w fit __launch_bounds__(512,8): <= 64 VGPRs, no
+//    scratch, 4 blocks/CU (tests/test_codeobject_occupancy.py holds them to
+//    that); k_dec_fwd_t<16> would spill there and stays at (512,6).
 //  * ping-pong LDS double buffer + register prefetch (guide T14/G15): ONE
 //    barrier per K-step; the NEXT K-tile's global loads issue before the
 //    MFMA phase of the current tile.
@@ -26,7 +35,7 @@
 //  * XCD-aware bijective block swizzle (guide T1): consecutive remapped
 //    blocks land on one XCD and share operand panels in its private L2.
 //
-// Kernels (each a template over TBK, MINW):
+// Kernels (each a template over TBK, MINW, TBN, ALIGNED):
 //   k_enc_fwd_t  : c = relu(x @ Wenc^T + b)    (+ L1 partial, fired counts)
 //   k_enc_fwd2_t : same with pre-transposed operands (all-direct staging)
 //   k_dec_fwd_t  : r = c @ Wdec_hat - x        (+ MSE partial)
@@ -40,6 +49,8 @@
 //   k_lista_bwd_elem (one-pass LISTA backward elementwise chain)
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 #define WAVE 64
 #define BM 128
@@ -93,7 +104,9 @@ struct TStage {
   float sc[TBK * TROWS / 2048];
 };
 
-template <int TBK, int TROWS = BM>
+// ALIGNED: the caller guarantees a full tile (no row or K tail) and 16-byte
+// aligned rows, so every load is one unguarded float4.
+template <int TBK, int TROWS = BM, bool ALIGNED = false>
 __device__ __forceinline__ void stage_T_load(const float* __restrict__ src, long ld,
                                              int i0, int k0, int n_rows, int n_k,
                                              const float* __restrict__ scale,
@@ -108,7 +121,10 @@ __device__ __forceinline__ void stage_T_load(const float* __restrict__ src, long
     int gi = i0 + i;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     float sc = 1.f;
-    if (gi < n_rows) {
+    if constexpr (ALIGNED) {
+      v = *reinterpret_cast<const float4*>(src + (long)gi * ld + k0 + kc);
+      if (scale) sc = scale[gi];
+    } else if (gi < n_rows) {
       const float* row = src + (long)gi * ld + k0 + kc;
       if (k0 + kc + 3 < n_k) {
         v = *reinterpret_cast<const float4*>(row);
@@ -150,7 +166,7 @@ struct DStage {
   float sc[TBK * TCOLS / 2048];
 };
 
-template <int TBK, int TCOLS = BM>
+template <int TBK, int TCOLS = BM, bool ALIGNED = false>
 __device__ __forceinline__ void stage_D_load(const float* __restrict__ src, long ld,
                                              int k0, int j0, int n_k, int n_cols,
                                              const float* __restrict__ scale,
@@ -165,7 +181,10 @@ __device__ __forceinline__ void stage_D_load(const float* __restrict__ src, long
     int gk = k0 + k;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
     float sc = 1.f;
-    if (gk < n_k) {
+    if constexpr (ALIGNED) {
+      v = *reinterpret_cast<const float4*>(src + (long)gk * ld + j0 + j);
+      if (scale) sc = scale[gk];
+    } else if (gk < n_k) {
       const float* row = src + (long)gk * ld + j0 + j;
       if (j0 + j + 3 < n_cols) {
         v = *reinterpret_cast<const float4*>(row);
@@ -253,6 +272,39 @@ __device__ __forceinline__ EpiGeom epi_geom() {
   return g;
 }
 
+// Index of accumulator element (tj, r) in a row-major [rows, ld] epilogue
+// operand.  The guarded kernels form it per element from (row, col).  ALIGNED
+// splits it into a block-uniform 64-bit part, which lives in scalar registers,
+// and one 32-bit offset per lane, so the 32 accesses of a thread share one
+// address VGPR instead of holding a 64-bit pair each (the launchers admit
+// ld < 2^23 only, so the lane part cannot wrap).
+template <bool ALIGNED>
+struct EpiIndex {
+  long tile;
+  unsigned lane_off;  // bytes
+  int ld;
+  __device__ __forceinline__ EpiIndex(int row0, int col0, int ld_, const EpiGeom& g) : ld(ld_) {
+    // row0/col0 are block-uniform but come out of a 64-bit division done in
+    // vector registers; readfirstlane moves them (and `tile`) to scalar ones
+    tile = (long)__builtin_amdgcn_readfirstlane(row0) * ld + __builtin_amdgcn_readfirstlane(col0);
+    lane_off = 4u * (unsigned)((g.wr + 4 * (g.lane >> 5)) * ld + g.wc + g.l31);
+  }
+  template <typename T>
+  __device__ __forceinline__ T& ref(T* base, int row, int col, int r, int tj) {
+    if constexpr (ALIGNED) {
+      T* pu = base + (tile + (long)((r & 3) + 8 * (r >> 2)) * ld + tj * 32);
+      // make lane_off opaque at every access (in place, no instruction):
+      // otherwise the compiler hoists base + lane_off into a 64-bit VGPR
+      // pointer and steps that per row
+      asm volatile("" : "+v"(lane_off));
+      using B = std::conditional_t<std::is_const_v<T>, const char, char>;
+      return *reinterpret_cast<T*>(reinterpret_cast<B*>(pu) + lane_off);
+    } else {
+      return base[(long)row * ld + col];
+    }
+  }
+};
+
 // ---------------------------------------------------------------------------
 // k_row_norms
 // ---------------------------------------------------------------------------
@@ -314,10 +366,23 @@ extern "C" __global__ void k_row_norms(const float* __restrict__ W,
 // sae_ensemble.py:256-259): u = (c + gain) / max(a^2, eps),
 // g(u) = relu6(60(u-0.9))/6 + relu(u-1), code = g(u) * a^2 (RAW a^2 — the
 // reference multiplies by the unclamped square).
+// Floating-point contraction is switched off in the epilogues below and every
+// fused multiply-add is written out: the guarded and the ALIGNED variant of a
+// kernel then round alike whatever the optimiser makes of either (left to
+// itself it fuses differently once the guards are gone).  The fmaf calls are
+// the contractions the guarded kernels were compiled with.
 #define GATE_EPS 1e-8f
 __device__ __forceinline__ float gate_g(float u) {
-  return fminf(fmaxf(60.0f * (u - 0.9f), 0.0f), 6.0f) * (1.0f / 6.0f) +
-         fmaxf(u - 1.0f, 0.0f);
+#pragma clang fp contract(off)
+  return fmaf(fminf(fmaxf(60.0f * (u - 0.9f), 0.0f), 6.0f), 1.0f / 6.0f,
+              fmaxf(u - 1.0f, 0.0f));
+}
+// g(x * s_inv) with the product folded into both subtractions (one rounding
+// each instead of two): the encoder epilogue's form
+__device__ __forceinline__ float gate_g_scaled(float x, float s_inv) {
+#pragma clang fp contract(off)
+  return fmaf(fminf(fmaxf(60.0f * fmaf(x, s_inv, -0.9f), 0.0f), 6.0f), 1.0f / 6.0f,
+              fmaxf(fmaf(x, s_inv, -1.0f), 0.0f));
 }
 __device__ __forceinline__ float gate_gp(float u) {  // dg/du (0 at the kinks)
   float gp = (u > 0.9f && u < 1.0f) ? 10.0f : 0.0f;
@@ -328,7 +393,7 @@ __device__ __forceinline__ float gate_gp(float u) {  // dg/du (0 at the kinks)
 // ---------------------------------------------------------------------------
 // k_enc_fwd_t
 // ---------------------------------------------------------------------------
-template <int TBK, int MINW, int TBN = BN>
+template <int TBK, int MINW, int TBN = BN, bool ALIGNED = false>
 __global__ __launch_bounds__(NTHREADS, MINW)
 void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
                  const float* __restrict__ Wenc,    // [M, n, d]
@@ -371,8 +436,8 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
   TStage<TBK> sa;
   TStage<TBK, TBN> sb;
 
-#define ENC_LA(K) stage_T_load<TBK>(x_m, d, row0, (K), B, d, nullptr, sa)
-#define ENC_LB(K) stage_T_load<TBK, TBN>(W, d, col0, (K), n, d, inv, sb)
+#define ENC_LA(K) stage_T_load<TBK, BM, ALIGNED>(x_m, d, row0, (K), B, d, nullptr, sa)
+#define ENC_LB(K) stage_T_load<TBK, TBN, ALIGNED>(W, d, col0, (K), n, d, inv, sb)
 #define ENC_WA(BUF) stage_T_write<TBK>(sa, &As[BUF][0], false)
 #define ENC_WB(BUF) stage_T_write<TBK, TBN>(sb, &Bs[BUF][0], scaled)
   PREFETCH_LOOP(TBK, d, ENC_LA, ENC_LB, ENC_WA, ENC_WB, BMP, TBN + 1)
@@ -382,6 +447,7 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
 #undef ENC_WB
 
   const EpiGeom g = epi_geom<NACC>();
+  EpiIndex<ALIGNED> ei(row0, col0, n, g);
   float* c_m = c_out + (long)m * B * n;
   const float* bias_m = bias + (long)m * n;
   float* fired_m = fired + (long)m * n;
@@ -389,14 +455,15 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
   float l1_sum = 0.f;
 #pragma unroll
   for (int tj = 0; tj < NACC; ++tj) {
+#pragma clang fp contract(off)
     int col = col0 + g.wc + tj * 32 + g.l31;
-    bool col_ok = col < n;
+    bool col_ok = ALIGNED || col < n;
     if (mode == 1) {
       // raw scores for TopK selection: no bias, no relu, no side outputs
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         int row = row0 + g.wr + acc_row(r, g.lane);
-        if (row < B && col_ok) c_m[(long)row * n + col] = acc[tj][r];
+        if ((ALIGNED || row < B) && col_ok) ei.ref(c_m, row, col, r, tj) = acc[tj][r];
       }
       continue;
     }
@@ -412,11 +479,16 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         int row = row0 + g.wr + acc_row(r, g.lane);
-        if (row < B && col_ok) {
-          float u = (acc[tj][r] + gn) * s_inv;
-          float code = gate_g(u) * s_raw;
-          c_m[(long)row * n + col] = code;
-          u_m[(long)row * n + col] = u;
+        if ((ALIGNED || row < B) && col_ok) {
+          float av = acc[tj][r];
+          // unguarded, the 16 gate chains of a column would be vectorised
+          // side by side, past the 64 registers of 8 waves/SIMD; an opaque
+          // accumulator value keeps them one after the other
+          if constexpr (ALIGNED) asm volatile("" : "+v"(av));
+          float u = (av + gn) * s_inv;
+          float code = gate_g_scaled(av + gn, s_inv) * s_raw;
+          ei.ref(c_m, row, col, r, tj) = code;
+          ei.ref(u_m, row, col, r, tj) = u;
           l1_sum += code;
           fired_cnt += (code > 0.f) ? 1.f : 0.f;
         }
@@ -448,17 +520,17 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         int row = row0 + g.wr + acc_row(r, g.lane);
-        if (row < B && col_ok) {
-          long idx = (long)row * n + col;
-          float v = y_m[idx] - acc[tj][r];
+        if ((ALIGNED || row < B) && col_ok) {
+          auto at = [&](auto* p) -> auto& { return ei.ref(p, row, col, r, tj); };
+          float v = at(y_m) - acc[tj][r];
           if (mode == 5) {
-            c_m[idx] = v;
+            at(c_m) = v;
           } else {
-            u_m[idx] = v;  // r_l, kept for the backward's shrink mask
+            at(u_m) = v;  // r_l, kept for the backward's shrink mask
             float a = fabsf(v) - th;
             float xa = (a > 0.f) ? ((v > 0.f) ? a : -a) : 0.f;
-            xo_m[idx] = xa;
-            c_m[idx] = xa + mm * (xa - xp_m[idx]);
+            at(xo_m) = xa;
+            at(c_m) = fmaf(mm, xa - at(xp_m), xa);
           }
         }
       }
@@ -473,10 +545,10 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         int row = row0 + g.wr + acc_row(r, g.lane);
-        if (row < B && col_ok) {
+        if ((ALIGNED || row < B) && col_ok) {
           float pre = acc[tj][r];
           float v = (pre + bj > 0.f) ? pre : 0.f;
-          c_m[(long)row * n + col] = v;
+          ei.ref(c_m, row, col, r, tj) = v;
           l1_sum += fabsf(v);
           fired_cnt += (v != 0.f) ? 1.f : 0.f;
         }
@@ -495,9 +567,9 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int row = row0 + g.wr + acc_row(r, g.lane);
-      if (row < B && col_ok) {
+      if ((ALIGNED || row < B) && col_ok) {
         float v = live ? fmaxf(acc[tj][r] + bj, 0.f) : 0.f;
-        c_m[(long)row * n + col] = v;
+        ei.ref(c_m, row, col, r, tj) = v;
         l1_sum += v;
         fired_cnt += (v > 0.f) ? 1.f : 0.f;
       }
@@ -517,7 +589,7 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
 // ---------------------------------------------------------------------------
 // k_dec_fwd_t
 // ---------------------------------------------------------------------------
-template <int TBK, int MINW, int TBN = BN>
+template <int TBK, int MINW, int TBN = BN, bool ALIGNED = false>
 __global__ __launch_bounds__(NTHREADS, MINW)
 void k_dec_fwd_t(const float* __restrict__ c,       // [M, B, n]
                  const float* __restrict__ Wdec,    // [M, n, d]
@@ -547,8 +619,8 @@ void k_dec_fwd_t(const float* __restrict__ c,       // [M, B, n]
   TStage<TBK> sa;
   DStage<TBK, TBN> sb;
 
-#define DEC_LA(K) stage_T_load<TBK>(c_m, n, row0, (K), B, n, nullptr, sa)
-#define DEC_LB(K) stage_D_load<TBK, TBN>(W, d, (K), col0, n, d, inv, sb)
+#define DEC_LA(K) stage_T_load<TBK, BM, ALIGNED>(c_m, n, row0, (K), B, n, nullptr, sa)
+#define DEC_LB(K) stage_D_load<TBK, TBN, ALIGNED>(W, d, (K), col0, n, d, inv, sb)
 #define DEC_WA(BUF) stage_T_write<TBK>(sa, &As[BUF][0], false)
 #define DEC_WB(BUF) stage_D_write<TBK, TBN>(sb, &Bs[BUF][0], true)
   PREFETCH_LOOP(TBK, n, DEC_LA, DEC_LB, DEC_WA, DEC_WB, BMP, TBN)
@@ -558,20 +630,22 @@ void k_dec_fwd_t(const float* __restrict__ c,       // [M, B, n]
 #undef DEC_WB
 
   const EpiGeom g = epi_geom<NACC>();
+  EpiIndex<ALIGNED> ei(row0, col0, d, g);
   float* r_m = r_out + (long)m * B * d;
 
   float mse_sum = 0.f;
 #pragma unroll
   for (int tj = 0; tj < NACC; ++tj) {
+#pragma clang fp contract(off)
     int col = col0 + g.wc + tj * 32 + g.l31;
-    bool col_ok = col < d;
+    bool col_ok = ALIGNED || col < d;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int row = row0 + g.wr + acc_row(r, g.lane);
-      if (row < B && col_ok) {
-        float rv = acc[tj][r] - x_m[(long)row * d + col];
-        r_m[(long)row * d + col] = rv;
-        mse_sum += rv * rv;
+      if ((ALIGNED || row < B) && col_ok) {
+        float rv = acc[tj][r] - ei.ref(x_m, row, col, r, tj);
+        ei.ref(r_m, row, col, r, tj) = rv;
+        mse_sum = fmaf(rv, rv, mse_sum);
       }
     }
   }
@@ -582,7 +656,7 @@ void k_dec_fwd_t(const float* __restrict__ c,       // [M, B, n]
 // ---------------------------------------------------------------------------
 // k_gc_t
 // ---------------------------------------------------------------------------
-template <int TBK, int MINW, int TBN = BN>
+template <int TBK, int MINW, int TBN = BN, bool ALIGNED = false>
 __global__ __launch_bounds__(NTHREADS, MINW)
 void k_gc_t(const float* __restrict__ r,        // [M, B, d]
             const float* __restrict__ Wdec,     // [M, n, d]
@@ -614,8 +688,8 @@ void k_gc_t(const float* __restrict__ r,        // [M, B, d]
   TStage<TBK> sa;
   TStage<TBK, TBN> sb;
 
-#define GC_LA(K) stage_T_load<TBK>(r_m, d, row0, (K), B, d, nullptr, sa)
-#define GC_LB(K) stage_T_load<TBK, TBN>(W, d, col0, (K), n, d, inv, sb)
+#define GC_LA(K) stage_T_load<TBK, BM, ALIGNED>(r_m, d, row0, (K), B, d, nullptr, sa)
+#define GC_LB(K) stage_T_load<TBK, TBN, ALIGNED>(W, d, col0, (K), n, d, inv, sb)
 #define GC_WA(BUF) stage_T_write<TBK>(sa, &As[BUF][0], false)
 #define GC_WB(BUF) stage_T_write<TBK, TBN>(sb, &Bs[BUF][0], true)
   PREFETCH_LOOP(TBK, d, GC_LA, GC_LB, GC_WA, GC_WB, BMP, TBN + 1)
@@ -625,6 +699,7 @@ void k_gc_t(const float* __restrict__ r,        // [M, B, d]
 #undef GC_WB
 
   const EpiGeom g = epi_geom<NACC>();
+  EpiIndex<ALIGNED> ei(row0, col0, n, g);
   float* g_m = gpre_out + (long)m * B * n;
   // bias grad: each wave owns one 32-row group of its columns and stores that
   // group's column sum with a plain store; k_colsum_groups adds the groups in
@@ -635,14 +710,15 @@ void k_gc_t(const float* __restrict__ r,        // [M, B, d]
 
 #pragma unroll
   for (int tj = 0; tj < NACC; ++tj) {
+#pragma clang fp contract(off)
     int col = col0 + g.wc + tj * 32 + g.l31;
-    bool col_ok = col < n;
+    bool col_ok = ALIGNED || col < n;
     float colsum = 0.f;
 #pragma unroll
     for (int r_ = 0; r_ < 16; ++r_) {
       int row = row0 + g.wr + acc_row(r_, g.lane);
-      if (row < B && col_ok) {
-        float cv = c_m[(long)row * n + col];
+      if ((ALIGNED || row < B) && col_ok) {
+        float cv = ei.ref(c_m, row, col, r_, tj);
         float gv;
         if (gc_mode == 1) {
           // reverse SAE: active set is cv != 0, l1 grad is sign(cv), and
@@ -650,16 +726,16 @@ void k_gc_t(const float* __restrict__ r,        // [M, B, d]
           float sgn = (cv > 0.f) ? 1.f : ((cv < 0.f) ? -1.f : 0.f);
           gv = (cv != 0.f) ? (gscale * acc[tj][r_] + l1_term * sgn) : 0.f;
         } else {
-          gv = (cv > 0.f) ? (gscale * acc[tj][r_] + l1_term) : 0.f;
+          gv = (cv > 0.f) ? fmaf(gscale, acc[tj][r_], l1_term) : 0.f;
         }
-        g_m[(long)row * n + col] = gv;
+        ei.ref(g_m, row, col, r_, tj) = gv;
         colsum += gv;
       }
     }
     if (col_ok && gc_mode == 0) {
       float other = __shfl_xor(colsum, 32, WAVE);
       float tot = colsum + other;
-      if (g.lane < 32 && rg < nrg) gb_m[col] = tot;
+      if (g.lane < 32 && (ALIGNED || rg < nrg)) gb_m[col] = tot;
     }
   }
 }
@@ -703,7 +779,7 @@ void k_colsum_groups(const float* __restrict__ part,  // [M, nrg, n]
 //   g_scale= sum_b dL/da = gv * 2a * (g(u) - [a^2>eps] g'(u) u a^2/max(..))
 // with gv = gscale*acc + l1/B * [code>0].
 // ---------------------------------------------------------------------------
-template <int TBK, int MINW, int TBN = BN>
+template <int TBK, int MINW, int TBN = BN, bool ALIGNED = false>
 __global__ __launch_bounds__(NTHREADS, MINW)
 void k_gc_thresh_t(const float* __restrict__ r,        // [M, B, d]
                    const float* __restrict__ Wdec,     // [M, n, d]
@@ -739,8 +815,8 @@ void k_gc_thresh_t(const float* __restrict__ r,        // [M, B, d]
   TStage<TBK> sa;
   TStage<TBK, TBN> sb;
 
-#define GCT_LA(K) stage_T_load<TBK>(r_m, d, row0, (K), B, d, nullptr, sa)
-#define GCT_LB(K) stage_T_load<TBK, TBN>(W, d, col0, (K), n, d, inv, sb)
+#define GCT_LA(K) stage_T_load<TBK, BM, ALIGNED>(r_m, d, row0, (K), B, d, nullptr, sa)
+#define GCT_LB(K) stage_T_load<TBK, TBN, ALIGNED>(W, d, col0, (K), n, d, inv, sb)
 #define GCT_WA(BUF) stage_T_write<TBK>(sa, &As[BUF][0], false)
 #define GCT_WB(BUF) stage_T_write<TBK, TBN>(sb, &Bs[BUF][0], true)
   PREFETCH_LOOP(TBK, d, GCT_LA, GCT_LB, GCT_WA, GCT_WB, BMP, TBN + 1)
@@ -750,14 +826,16 @@ void k_gc_thresh_t(const float* __restrict__ r,        // [M, B, d]
 #undef GCT_WB
 
   const EpiGeom g = epi_geom<NACC>();
+  EpiIndex<ALIGNED> ei(row0, col0, n, g);
   float* g_m = gpre_out + (long)m * B * n;
   float* gg_m = g_gain + (long)m * n;
   float* gs_m = g_scale + (long)m * n;
 
 #pragma unroll
   for (int tj = 0; tj < NACC; ++tj) {
+#pragma clang fp contract(off)
     int col = col0 + g.wc + tj * 32 + g.l31;
-    bool col_ok = col < n;
+    bool col_ok = ALIGNED || col < n;
     float a = col_ok ? act_scale[(long)m * n + col] : 1.f;
     float s_raw = a * a;
     float s = fmaxf(s_raw, GATE_EPS);
@@ -767,14 +845,14 @@ void k_gc_thresh_t(const float* __restrict__ r,        // [M, B, d]
 #pragma unroll
     for (int r_ = 0; r_ < 16; ++r_) {
       int row = row0 + g.wr + acc_row(r_, g.lane);
-      if (row < B && col_ok) {
-        long idx = (long)row * n + col;
-        float code = c_m[idx];
-        float uv = u_m[idx];
+      if ((ALIGNED || row < B) && col_ok) {
+        auto at = [&](auto* p) -> auto& { return ei.ref(p, row, col, r_, tj); };
+        float code = at(c_m);
+        float uv = at(u_m);
         float gp = gate_gp(uv);
-        float gv = gscale * acc[tj][r_] + ((code > 0.f) ? l1_term : 0.f);
+        float gv = fmaf(gscale, acc[tj][r_], (code > 0.f) ? l1_term : 0.f);
         float gc_ = gv * gp * f;
-        g_m[idx] = gc_;
+        at(g_m) = gc_;
         gain_colsum += gc_;
         scale_colsum += gv * 2.0f * a * (gate_g(uv) - clamp_act * gp * uv * f);
       }
@@ -940,7 +1018,7 @@ void k_topk_select(const float* __restrict__ scores,  // [M, B, n]
 // ---------------------------------------------------------------------------
 // k_grad_w_t
 // ---------------------------------------------------------------------------
-template <int TBK, int MINW, int TBN = BN>
+template <int TBK, int MINW, int TBN = BN, bool ALIGNED = false>
 __global__ __launch_bounds__(NTHREADS, MINW)
 void k_grad_w_t(const float* __restrict__ P, long p_batch_stride,
                 const float* __restrict__ Q, long q_batch_stride,
@@ -965,8 +1043,8 @@ void k_grad_w_t(const float* __restrict__ P, long p_batch_stride,
   DStage<TBK> sa;
   DStage<TBK, TBN> sb;
 
-#define GW_LA(K) stage_D_load<TBK>(P_m, n, (K), row0, B, n, nullptr, sa)
-#define GW_LB(K) stage_D_load<TBK, TBN>(Q_m, d, (K), col0, B, d, nullptr, sb)
+#define GW_LA(K) stage_D_load<TBK, BM, ALIGNED>(P_m, n, (K), row0, B, n, nullptr, sa)
+#define GW_LB(K) stage_D_load<TBK, TBN, ALIGNED>(Q_m, d, (K), col0, B, d, nullptr, sb)
 #define GW_WA(BUF) stage_D_write<TBK>(sa, &As[BUF][0], false)
 #define GW_WB(BUF) stage_D_write<TBK, TBN>(sb, &Bs[BUF][0], false)
   PREFETCH_LOOP(TBK, B, GW_LA, GW_LB, GW_WA, GW_WB, BM, TBN)
@@ -976,20 +1054,22 @@ void k_grad_w_t(const float* __restrict__ P, long p_batch_stride,
 #undef GW_WB
 
   const EpiGeom g = epi_geom<NACC>();
+  EpiIndex<ALIGNED> ei(row0, col0, d, g);
   float* gw_m = gw + (long)m * n * d;
 
 #pragma unroll
   for (int tj = 0; tj < NACC; ++tj) {
+#pragma clang fp contract(off)
     int col = col0 + g.wc + tj * 32 + g.l31;
-    bool col_ok = col < d;
+    bool col_ok = ALIGNED || col < d;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       int row = row0 + g.wr + acc_row(r, g.lane);
-      if (row < n && col_ok) {
-        long idx = (long)row * d + col;
+      if ((ALIGNED || row < n) && col_ok) {
+        auto at = [&](auto* p) -> auto& { return ei.ref(p, row, col, r, tj); };
         float v = alpha * acc[tj][r];
-        if (beta != 0.f) v += beta * gw_m[idx];
-        gw_m[idx] = v;
+        if (beta != 0.f) v = fmaf(beta, at(gw_m), v);
+        at(gw_m) = v;
       }
     }
   }

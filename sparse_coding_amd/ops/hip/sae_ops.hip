@@ -19,22 +19,68 @@ static inline hipStream_t cur_stream() {
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 
 // Tile dispatch for the GEMM launchers, stated once.  The kernels are
-// instantiated as <TBK, MINW[, TBN]>: <16, 6> and <32, 4> are the two depths
+// instantiated as <TBK, MINW, TBN, ALIGNED>: TBK 16 and 32 are the two depths
 // of the 128x128 tile, <16, 4, 256> is the 128x256 tile.  LAUNCH_TILE picks by
 // tile depth alone (kernels without a 256-wide variant); LAUNCH_TILE_BN takes
 // the 256-wide one when bn == 256.  Each launcher states its grid and its
 // argument list once.
+//
+// Every variant exists twice.  The guarded kernels take any shape.  The
+// ALIGNED ones drop every row, column and K-tail guard, and are launched when
+// the TileShape says that no guard could fire: rows % 128 == 0, cols % TBN ==
+// 0, K % TBK == 0, the float4-staged operands 16-byte aligned with leading
+// dimensions that are multiples of 4.  `mw16` is the aligned TBK=16 kernel's
+// minimum waves per SIMD: 8 (four workgroups per CU) where it compiles to
+// <= 64 VGPRs without scratch, else the guarded kernel's 6.
+struct TileShape {
+  long rows, cols, K;  // of the GEMM: output rows and columns, contraction
+  bool operands_ok;    // base pointers and leading dimensions
+  bool aligned(int tbn, int tbk) const {
+    return operands_ok && rows % BM == 0 && cols % tbn == 0 && K % tbk == 0;
+  }
+};
+
+static bool g_aligned_tiles = true;
+void set_aligned_tiles(bool on) { g_aligned_tiles = on; }
+bool aligned_tiles() { return g_aligned_tiles; }
+
+// operands of one launch: a and b are staged with float4 loads, ld_out is the
+// leading dimension of the epilogue's row-major operands (its per-lane byte
+// offset, at most 4 * (127 * ld_out + 255), is kept in 32 bits)
+static inline TileShape tile_shape(long rows, long cols, long K,
+                                   const void* a, long lda, const void* b, long ldb,
+                                   long ld_out) {
+  auto ok = [](const void* p, long ld) {
+    return reinterpret_cast<uintptr_t>(p) % 16 == 0 && ld % 4 == 0;
+  };
+  return {rows, cols, K,
+          g_aligned_tiles && ok(a, lda) && ok(b, ldb) && ld_out < (1L << 23)};
+}
+
 #define LAUNCH_AS(kern, grid, ...) \
   hipLaunchKernelGGL(kern, grid, dim3(NTHREADS), 0, cur_stream(), __VA_ARGS__)
-#define LAUNCH_TILE(kern, bk, grid, ...)                          \
+#define LAUNCH_VARIANT(kern, tbk, mw, mw_aligned, tbn, shape, grid, ...)         \
+  do {                                                                            \
+    if ((shape).aligned(tbn, tbk))                                                \
+      LAUNCH_AS((kern<tbk, mw_aligned, tbn, true>), grid, __VA_ARGS__);           \
+    else                                                                          \
+      LAUNCH_AS((kern<tbk, mw, tbn, false>), grid, __VA_ARGS__);                  \
+  } while (0)
+#define LAUNCH_TILE(kern, mw16, shape, bk, grid, ...)                             \
+  do {                                                                            \
+    if ((bk) == 16) LAUNCH_VARIANT(kern, 16, 6, mw16, BN, shape, grid, __VA_ARGS__); \
+    else LAUNCH_VARIANT(kern, 32, 4, 4, BN, shape, grid, __VA_ARGS__);            \
+  } while (0)
+#define LAUNCH_TILE_BN(kern, mw16, shape, bn, bk, grid, ...)                      \
+  do {                                                                            \
+    if ((bn) == 256) LAUNCH_VARIANT(kern, 16, 4, 4, 256, shape, grid, __VA_ARGS__); \
+    else LAUNCH_TILE(kern, mw16, shape, bk, grid, __VA_ARGS__);                   \
+  } while (0)
+// the pre-transposed pair has no aligned variants
+#define LAUNCH_TILE_GUARDED(kern, bk, grid, ...)                  \
   do {                                                            \
     if ((bk) == 16) LAUNCH_AS((kern<16, 6>), grid, __VA_ARGS__);  \
     else LAUNCH_AS((kern<32, 4>), grid, __VA_ARGS__);             \
-  } while (0)
-#define LAUNCH_TILE_BN(kern, bn, bk, grid, ...)                           \
-  do {                                                                    \
-    if ((bn) == 256) LAUNCH_AS((kern<16, 4, 256>), grid, __VA_ARGS__);    \
-    else LAUNCH_TILE(kern, bk, grid, __VA_ARGS__);                        \
   } while (0)
 
 void row_norms(torch::Tensor W, torch::Tensor norms, torch::Tensor inv_norms, double eps) {
@@ -111,7 +157,8 @@ void enc_fwd(torch::Tensor x, torch::Tensor Wenc, torch::Tensor bias,
     }
   }
   dim3 grid(cdiv(n, bn == 256 ? 256 : BN), cdiv(B, BM), M);
-  LAUNCH_TILE_BN(k_enc_fwd_t, bn, bk, grid,
+  const TileShape shape = tile_shape(B, n, d, x.data_ptr<float>(), d, Wenc.data_ptr<float>(), d, n);
+  LAUNCH_TILE_BN(k_enc_fwd_t, 8, shape, bn, bk, grid,
                  x.data_ptr<float>(), Wenc.data_ptr<float>(),
                  bias.data_ptr<float>(), inv, c_out.data_ptr<float>(),
                  loss_parts.data_ptr<float>(), fired.data_ptr<float>(),
@@ -132,7 +179,9 @@ void dec_fwd(torch::Tensor c, torch::Tensor Wdec, torch::Tensor inv_norms,
   }
   int B = x.size(x.dim() - 2);
   dim3 grid(cdiv(d, bn == 256 ? 256 : BN), cdiv(B, BM), M);
-  LAUNCH_TILE_BN(k_dec_fwd_t, bn, bk, grid,
+  const TileShape shape = tile_shape(B, d, n, c.data_ptr<float>(), n, Wdec.data_ptr<float>(), d, d);
+  // the aligned TBK=16 kernel needs scratch at 8 waves/SIMD: it keeps 6
+  LAUNCH_TILE_BN(k_dec_fwd_t, 6, shape, bn, bk, grid,
                  c.data_ptr<float>(), Wdec.data_ptr<float>(),
                  inv_norms.data_ptr<float>(), x.data_ptr<float>(),
                  r_out.data_ptr<float>(), loss_parts.data_ptr<float>(),
@@ -159,7 +208,8 @@ void gc(torch::Tensor r, torch::Tensor Wdec, torch::Tensor inv_norms,
     part = torch::empty({M, nrg, n}, r.options());
     part_p = part.data_ptr<float>();
   }
-  LAUNCH_TILE_BN(k_gc_t, bn, bk, grid,
+  const TileShape shape = tile_shape(B, n, d, r.data_ptr<float>(), d, Wdec.data_ptr<float>(), d, n);
+  LAUNCH_TILE_BN(k_gc_t, 8, shape, bn, bk, grid,
                  r.data_ptr<float>(), Wdec.data_ptr<float>(),
                  inv_norms.data_ptr<float>(), c.data_ptr<float>(),
                  l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
@@ -182,7 +232,8 @@ void gc_thresh(torch::Tensor r, torch::Tensor Wdec, torch::Tensor inv_norms,
   int M = Wdec.size(0), n = Wdec.size(1), d = Wdec.size(2);
   int B = r.size(1);
   dim3 grid(cdiv(n, BN), cdiv(B, BM), M);
-  LAUNCH_TILE(k_gc_thresh_t, bk, grid,
+  const TileShape shape = tile_shape(B, n, d, r.data_ptr<float>(), d, Wdec.data_ptr<float>(), d, n);
+  LAUNCH_TILE(k_gc_thresh_t, 8, shape, bk, grid,
               r.data_ptr<float>(), Wdec.data_ptr<float>(),
               inv_norms.data_ptr<float>(), c.data_ptr<float>(),
               u.data_ptr<float>(), act_scale.data_ptr<float>(),
@@ -207,7 +258,8 @@ void grad_w(torch::Tensor P, torch::Tensor Q, torch::Tensor gw,
     q_stride = 0;  // shared across models
   }
   dim3 grid(cdiv(d, bn == 256 ? 256 : BN), cdiv(n, BM), M);
-  LAUNCH_TILE_BN(k_grad_w_t, bn, bk, grid,
+  const TileShape shape = tile_shape(n, d, B, P.data_ptr<float>(), n, Q.data_ptr<float>(), d, d);
+  LAUNCH_TILE_BN(k_grad_w_t, 8, shape, bn, bk, grid,
                  P.data_ptr<float>(), p_stride, Q.data_ptr<float>(),
                  q_stride, gw.data_ptr<float>(), (float)alpha,
                  (float)beta, B, n, d, prio ? 1 : 0);
@@ -317,7 +369,7 @@ void enc_fwd2(torch::Tensor xT, torch::Tensor WT, torch::Tensor bias,
     ds_p = dict_sizes->data_ptr<int>();
   }
   dim3 grid(cdiv(n, BN), cdiv(B, BM), M);
-  LAUNCH_TILE(k_enc_fwd2_t, bk, grid,
+  LAUNCH_TILE_GUARDED(k_enc_fwd2_t, bk, grid,
               xT.data_ptr<float>(), WT.data_ptr<float>(),
               bias.data_ptr<float>(), c_out.data_ptr<float>(),
               loss_parts.data_ptr<float>(), fired.data_ptr<float>(),
@@ -332,7 +384,7 @@ void gc2(torch::Tensor rT, torch::Tensor WT, torch::Tensor c,
   int M = WT.size(0), d = WT.size(1), n = WT.size(2);
   int B = rT.size(2);
   dim3 grid(cdiv(n, BN), cdiv(B, BM), M);
-  LAUNCH_TILE(k_gc2_t, bk, grid,
+  LAUNCH_TILE_GUARDED(k_gc2_t, bk, grid,
               rT.data_ptr<float>(), WT.data_ptr<float>(),
               c.data_ptr<float>(), l1_alpha.data_ptr<float>(),
               gpre.data_ptr<float>(), g_bias.data_ptr<float>(),
@@ -409,6 +461,10 @@ void lista_bwd_elem(torch::Tensor g_y, c10::optional<torch::Tensor> carry_in,
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
+  m.def("set_aligned_tiles", &set_aligned_tiles,
+        "process-wide switch: launch the guard-free GEMM kernels on tile-aligned shapes (default on)",
+        py::arg("on"));
+  m.def("aligned_tiles", &aligned_tiles, "whether tile-aligned launches take the guard-free kernels");
   m.def("row_norms", &row_norms, "dictionary row norms + clamped inverses");
   m.def("transpose_scale", &transpose_scale, "batched [R,C]->[C,R] transpose with row scale");
   m.def("enc_fwd2", &enc_fwd2, "enc forward, pre-transposed operands (all-direct staging)",

@@ -2,9 +2,16 @@
 
 The GEMM kernels are compiled in two tile depths (see sae_kernels.hip):
 
-  bk=32  128x128 tile, 64-66 KB LDS, 2 blocks/CU  (default)
-  bk=16  128x128 tile, 32-33 KB LDS, 3 blocks/CU  (more co-resident blocks
-         to hide barrier skew; <=80 VGPRs via __launch_bounds__(512, 6))
+  bk=32  128x128 tile, 64-66 KB LDS, 2 blocks/CU
+  bk=16  128x128 tile, 32-33 KB LDS  (default; more co-resident blocks to hide
+         barrier skew).  The guarded kernels (__launch_bounds__(512, 6),
+         69-70 VGPRs = 7 waves/SIMD) fit 3 blocks/CU.  On tile-aligned launches
+         (rows % 128 == 0, cols % tile width == 0, K % bk == 0, 16-byte aligned
+         operands) the launchers take guard-free variants of enc_fwd, gc,
+         gc_thresh and grad_w compiled with __launch_bounds__(512, 8):
+         <= 64 VGPRs, no scratch, 4 blocks/CU.  dec_fwd's bk=16 variant stays
+         at 3 (it would spill at 64 registers).  The extension's
+         set_aligned_tiles(False) sends every launch to the guarded kernels.
 
 plus a `prio` flag (s_setprio(1) on the second-dispatched wave half) and a
 `staging` choice for the encoder/code-grad GEMMs:
@@ -33,13 +40,14 @@ import os
 # Measured winners (MI355X, flagship bench shape; see profiles/README.md).
 DEFAULTS = {
     # ktune sweep r01 (profiles/README.md): t/bk16 639k acts/s vs t/bk32
-    # 628k, pre/bk16 632k, pre/bk32 629k; prio neutral.  bk16 = 4 blocks/CU.
+    # 628k, pre/bk16 632k, pre/bk32 629k; prio neutral.  bk16 = 3 blocks/CU
+    # guarded, 4 on tile-aligned launches (module docstring).
     "bk": 16,
     "prio": False,
     "staging": "t",
     # output-tile width of the GEMM kernels: 128 (default) or 256
     # (128x256 tiles: 4 accumulators/wave, 2 blocks/CU — measured slower
-    # than bk16's 4-block co-residency on the flagship shape, kept as a
+    # than bk16's 3-block co-residency on the flagship shape, kept as a
     # variant; see profiles/README.md)
     "bn": 128,
     # per-kernel overrides, None -> use "bk".  dec_fwd reduces over the
