@@ -12,9 +12,14 @@
 //    quadrant as 2 v_mfma_f32_32x32x2_f32 accumulators (32 AGPRs).
 //  * K-tile depth TBK is a template parameter:
 //      TBK=32, __launch_bounds__(512,4): 64-66 KB LDS, 2 blocks/CU.
-//      TBK=16, __launch_bounds__(512,6): 32-33 KB LDS, 69-70 VGPRs,
-//        3 blocks/CU — more co-resident blocks to hide barrier skew
-//        (SQ_WAIT_ANY was 25-33% of wave cycles at 2 blocks/CU).
+//      TBK=16, __launch_bounds__(512,6): 32-33 KB LDS — more co-resident
+//        blocks to hide barrier skew (SQ_WAIT_ANY was 25-33% of wave cycles
+//        at 2 blocks/CU).  The bound asks for 3 blocks/CU; what runs follows
+//        from the registers (an 8-wave block takes 2 wave slots per SIMD):
+//        guarded enc, gc, gc_thresh and dec take 69-71 VGPRs = 7 waves/SIMD
+//        = 3 blocks/CU; guarded grad_w, enc_fwd2 and gc2 take 60-62 and fit
+//        4 blocks/CU (derived from the code object's metadata, not observed
+//        on the device; per-kernel table: profiles/README.md, r04).
 //    Both are compiled; the launcher picks at runtime (ops.kconfig).
 //  * ALIGNED template flag: every GEMM kernel also exists without its row,
 //    column and K-tail guards (plain float4 staging loads, unguarded epilogue
@@ -34,6 +39,22 @@
 //    `prio` flag; MI355X_MICROARCH "Two waves per SIMD" item 4).
 //  * XCD-aware bijective block swizzle (guide T1): consecutive remapped
 //    blocks land on one XCD and share operand panels in its private L2.
+//
+// The seven GEMM kernels share one skeleton, written once as device functions:
+//   Tile<TBN>            prologue: priority, model, swizzled tile, zeroed acc
+//   TStage/TLds, DStage/DLds   one operand's registers in flight and its LDS
+//                        buffers; the LDS type owns extent and stride
+//   gemm_mainloop        the prefetch K-loop; the kernel passes its two loads
+//                        and two LDS writes as lambdas (k_gc_t alone writes
+//                        the loop out: measured slower through the function)
+//   epi_cols / epi_rows  the epilogue's walk over the accumulators, with the
+//                        guards and the element accessor `at` (k_gc_t and
+//                        k_gc_thresh_t write the same walk out: the helpers
+//                        cost their 8-waves/SIMD variants a register and time)
+//   halfwave_pair_sum    per-column sum across the two half-waves
+// A kernel body holds its operand pointers, its four staging lambdas and its
+// per-element / per-column epilogue arithmetic.  The epilogues switch
+// floating-point contraction off (k_enc_fwd2_t/k_gc2_t excepted: guarded only).
 //
 // Kernels (each a template over TBK, MINW, TBN, ALIGNED):
 //   k_enc_fwd_t  : c = relu(x @ Wenc^T + b)    (+ L1 partial, fired counts)
@@ -55,7 +76,6 @@
 #define WAVE 64
 #define BM 128
 #define BN 128
-#define BMP (BM + 1)  // padded LDS stride for transposed staging
 #define NTHREADS 512
 #define NXCD 8
 
@@ -97,11 +117,22 @@ __device__ __forceinline__ void maybe_prio(int prio) {
 // overlap the previous tile's MFMA phase.  TBK/16 float4 passes per thread.
 // ---------------------------------------------------------------------------
 
+// Each operand layout comes as a pair: the registers of one tile in flight
+// (TStage/DStage) and its ping-pong LDS buffers (TLds/DLds).  The LDS type owns
+// the extent and the row stride; stage_*_write accepts only the matching type
+// and mfma_tile reads STRIDE from it, so a kernel states a layout once, in its
+// __shared__ declaration, and the three cannot disagree.
+
 // Transposed tile: lds[k][i] = src[i0+i][k0+k] (* scale[i0+i]), i<TROWS, k<TBK.
 template <int TBK, int TROWS = BM>
 struct TStage {
   float4 v[TBK * TROWS / 2048];
   float sc[TBK * TROWS / 2048];
+};
+template <int TBK, int TROWS = BM>
+struct TLds {
+  static constexpr int STRIDE = TROWS + 1;  // padded: conflict-free b32 writes
+  float buf[2][TBK * STRIDE];
 };
 
 // ALIGNED: the caller guarantees a full tile (no row or K tail) and 16-byte
@@ -140,9 +171,10 @@ __device__ __forceinline__ void stage_T_load(const float* __restrict__ src, long
   }
 }
 
-template <int TBK, int TROWS = BM>
-__device__ __forceinline__ void stage_T_write(const TStage<TBK, TROWS>& st, float* __restrict__ lds,
-                                              bool scaled) {
+template <int TBK, int TROWS>
+__device__ __forceinline__ void stage_T_write(const TStage<TBK, TROWS>& st, TLds<TBK, TROWS>& dst,
+                                              int buf, bool scaled) {
+  float* __restrict__ lds = dst.buf[buf];
   const int t = threadIdx.x;
   constexpr int TPR = TBK / 4;
   constexpr int RPP = NTHREADS / TPR;
@@ -155,7 +187,7 @@ __device__ __forceinline__ void stage_T_write(const TStage<TBK, TROWS>& st, floa
       v.x *= st.sc[p]; v.y *= st.sc[p]; v.z *= st.sc[p]; v.w *= st.sc[p];
     }
 #pragma unroll
-    for (int s = 0; s < 4; ++s) lds[(kc + s) * (TROWS + 1) + i] = ((float*)&v)[s];
+    for (int s = 0; s < 4; ++s) lds[(kc + s) * TLds<TBK, TROWS>::STRIDE + i] = ((float*)&v)[s];
   }
 }
 
@@ -164,6 +196,11 @@ template <int TBK, int TCOLS = BM>
 struct DStage {
   float4 v[TBK * TCOLS / 2048];
   float sc[TBK * TCOLS / 2048];
+};
+template <int TBK, int TCOLS = BM>
+struct DLds {
+  static constexpr int STRIDE = TCOLS;  // float4 (b128) writes
+  float buf[2][TBK * STRIDE];
 };
 
 template <int TBK, int TCOLS = BM, bool ALIGNED = false>
@@ -200,9 +237,10 @@ __device__ __forceinline__ void stage_D_load(const float* __restrict__ src, long
   }
 }
 
-template <int TBK, int TCOLS = BM>
-__device__ __forceinline__ void stage_D_write(const DStage<TBK, TCOLS>& st, float* __restrict__ lds,
-                                              bool scaled) {
+template <int TBK, int TCOLS>
+__device__ __forceinline__ void stage_D_write(const DStage<TBK, TCOLS>& st, DLds<TBK, TCOLS>& dst,
+                                              int buf, bool scaled) {
+  float* __restrict__ lds = dst.buf[buf];
   const int t = threadIdx.x;
   constexpr int TPC = TCOLS / 4;
   constexpr int KPP = NTHREADS / TPC;
@@ -214,7 +252,7 @@ __device__ __forceinline__ void stage_D_write(const DStage<TBK, TCOLS>& st, floa
     if (scaled) {
       v.x *= st.sc[p]; v.y *= st.sc[p]; v.z *= st.sc[p]; v.w *= st.sc[p];
     }
-    *reinterpret_cast<float4*>(&lds[k * TCOLS + j]) = v;
+    *reinterpret_cast<float4*>(&lds[k * DLds<TBK, TCOLS>::STRIDE + j]) = v;
   }
 }
 
@@ -224,7 +262,7 @@ __device__ __forceinline__ void stage_D_write(const DStage<TBK, TCOLS>& st, floa
 template <int TBK, int NACC, int ASTRIDE, int BSTRIDE>
 __device__ __forceinline__ void mfma_tile(const float* __restrict__ As,
                                           const float* __restrict__ Bs,
-                                          f32x16 acc[NACC]) {
+                                          f32x16 (&acc)[NACC]) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int wave = threadIdx.x / WAVE;
   const int wr = (wave & 3) * 32;
@@ -243,13 +281,59 @@ __device__ __forceinline__ void mfma_tile(const float* __restrict__ As,
   }
 }
 
-template <int NACC>
-__device__ __forceinline__ void zero_acc(f32x16 acc[NACC]) {
-#pragma unroll
-  for (int j = 0; j < NACC; ++j)
-#pragma unroll
-    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+// Ping-pong double buffer + register prefetch: ONE barrier per K-step.
+// Iteration t: issue loads of tile t+1, MFMA on buffer `cur` (tile t), write
+// tile t+1 into buffer cur^1 (nobody reads it), barrier, flip.  The barrier
+// at the end of iteration t also protects the write of tile t+2 into the
+// old `cur` (every wave has finished reading it).
+// load_a/load_b(k0) fetch the K-tile at k0 into the kernel's stage registers,
+// write_a/write_b(buf) store those registers into LDS buffer `buf`.
+// k_gc_t holds a written-out copy of this loop (the reason is stated there):
+// a change to the order of operations here has to be made there too.
+template <int TBK, int NACC, class ALds, class BLds, class LoadA, class LoadB, class WriteA,
+          class WriteB>
+__device__ __forceinline__ void gemm_mainloop(int k_total, ALds& As, BLds& Bs, f32x16 (&acc)[NACC],
+                                              LoadA load_a, LoadB load_b, WriteA write_a,
+                                              WriteB write_b) {
+  constexpr int ASTR = ALds::STRIDE, BSTR = BLds::STRIDE;
+  int cur = 0;
+  load_a(0);
+  load_b(0);
+  write_a(0);
+  write_b(0);
+  __syncthreads();
+  for (int k0 = TBK; k0 < k_total; k0 += TBK) {
+    load_a(k0);
+    load_b(k0);
+    mfma_tile<TBK, NACC, ASTR, BSTR>(As.buf[cur], Bs.buf[cur], acc);
+    write_a(cur ^ 1);
+    write_b(cur ^ 1);
+    __syncthreads();
+    cur ^= 1;
+  }
+  mfma_tile<TBK, NACC, ASTR, BSTR>(As.buf[cur], Bs.buf[cur], acc);
 }
+
+// Where a GEMM kernel starts: wave priority, this block's model and (swizzled)
+// output tile, and the zeroed accumulators of a BM x TBN tile.
+template <int TBN>
+struct Tile {
+  static constexpr int NACC = TBN / 64;
+  int m, row0, col0;
+  f32x16 acc[NACC];
+  __device__ __forceinline__ explicit Tile(int prio) {
+    maybe_prio(prio);
+    m = blockIdx.z;
+    int tx, ty;
+    tile_coords(tx, ty);
+    row0 = ty * BM;
+    col0 = tx * TBN;
+#pragma unroll
+    for (int j = 0; j < NACC; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+  }
+};
 
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll
@@ -305,6 +389,44 @@ struct EpiIndex {
   }
 };
 
+// The epilogue's walk over a thread's accumulators, shared by the GEMM kernels
+// (k_gc_t and k_gc_thresh_t write it out, see there): NACC column blocks (one
+// column per lane each), 16 rows per block.
+// A kernel's epilogue is per_col(tj, col, col_ok) holding its per-column head
+// and tail around one epi_rows call; per_elem(r, at) runs for the in-range
+// elements, with at(p) the element's slot in a row-major [rows, ld] operand.
+// A `#pragma clang fp contract(off)` at the top of a per_col lambda reaches
+// the lambdas defined inside it (checked on the ISA: mul + add, no fma).
+template <int NACC, bool ALIGNED, class PerCol>
+__device__ __forceinline__ void epi_cols(const EpiGeom& g, int col0, int n_cols, PerCol per_col) {
+#pragma unroll
+  for (int tj = 0; tj < NACC; ++tj) {
+    int col = col0 + g.wc + tj * 32 + g.l31;
+    per_col(tj, col, ALIGNED || col < n_cols);
+  }
+}
+
+template <bool ALIGNED, class PerElem>
+__device__ __forceinline__ void epi_rows(const EpiGeom& g, EpiIndex<ALIGNED>& ei, int row0,
+                                         int n_rows, int tj, int col, bool col_ok,
+                                         PerElem per_elem) {
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    int row = row0 + g.wr + acc_row(r, g.lane);
+    if ((ALIGNED || row < n_rows) && col_ok)
+      per_elem(r, [&](auto* p) -> auto& { return ei.ref(p, row, col, r, tj); });
+  }
+}
+
+// A column of a wave's 32x32 block lives in lanes l and l+32 (rows 4h..4h+3 of
+// every 8, h = lane>>5).  tot = this lane's partial + the other half-wave's;
+// true for the lane that owns the column's store or atomic (lane < 32).
+__device__ __forceinline__ bool halfwave_pair_sum(const EpiGeom& g, float v, float& tot) {
+  float other = __shfl_xor(v, 32, WAVE);
+  tot = v + other;
+  return g.lane < 32;
+}
+
 // ---------------------------------------------------------------------------
 // k_row_norms
 // ---------------------------------------------------------------------------
@@ -334,33 +456,20 @@ extern "C" __global__ void k_row_norms(const float* __restrict__ W,
   }
 }
 
-// ---------------------------------------------------------------------------
-// the shared prefetch K-loop (macro: operands differ per kernel)
-// ---------------------------------------------------------------------------
-// Ping-pong double buffer + register prefetch: ONE barrier per K-step.
-// Iteration t: issue loads of tile t+1, MFMA on buffer `cur` (tile t), write
-// tile t+1 into buffer cur^1 (nobody reads it), barrier, flip.  The barrier
-// at the end of iteration t also protects the write of tile t+2 into the
-// old `cur` (every wave has finished reading it).
-#define PREFETCH_LOOP(TBK, K_TOTAL, LOAD_A, LOAD_B, WRITE_A, WRITE_B, ASTR, BSTR) \
-  {                                                                            \
-    int cur = 0;                                                               \
-    LOAD_A(0);                                                                 \
-    LOAD_B(0);                                                                 \
-    WRITE_A(0);                                                                \
-    WRITE_B(0);                                                                \
-    __syncthreads();                                                           \
-    for (int k0 = (TBK); k0 < (K_TOTAL); k0 += (TBK)) {                        \
-      LOAD_A(k0);                                                              \
-      LOAD_B(k0);                                                              \
-      mfma_tile<TBK, NACC, ASTR, BSTR>(&As[cur][0], &Bs[cur][0], acc);         \
-      WRITE_A(cur ^ 1);                                                        \
-      WRITE_B(cur ^ 1);                                                        \
-      __syncthreads();                                                         \
-      cur ^= 1;                                                                \
-    }                                                                          \
-    mfma_tile<TBK, NACC, ASTR, BSTR>(&As[cur][0], &Bs[cur][0], acc);           \
-  }
+// Epilogue selectors of k_enc_fwd_t/k_enc_fwd2_t (`mode`) and k_gc_t/k_gc2_t
+// (`gc_mode`); the values are the integers the Python side passes.
+enum EncMode : int {
+  ENC_RELU = 0,       // c = relu(acc + b), masked by dict_sizes (+L1, fired)
+  ENC_RAW = 1,        // raw scores for TopK selection
+  ENC_GATE = 2,       // thresholding SAE's soft gate (+L1, fired, u)
+  ENC_REVERSE = 3,    // reverse SAE: c = acc * [acc + b > 0] (+L1, fired)
+  ENC_LISTA_FWD = 4,  // LISTA layer: shrink + momentum
+  ENC_LISTA_BWD = 5,  // LISTA backward: c = y_in - acc
+};
+enum GcMode : int {
+  GC_RELU = 0,     // active set c > 0, bias gradient produced
+  GC_REVERSE = 1,  // reverse SAE: active set c != 0, sign(c) l1 term, no bias grad
+};
 
 // The soft-threshold gate of the thresholding SAE (reference
 // sae_ensemble.py:256-259): u = (c + gain) / max(a^2, eps),
@@ -403,8 +512,7 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
                  float* __restrict__ loss_parts,    // [M, 2]
                  float* __restrict__ fired,         // [M, n]
                  int B, int d, int n,
-                 int mode,  // 0: bias+relu (+L1/fired); 1: raw scores (TopK);
-                            // 2: threshold gate via act_scale/act_gain/u_out
+                 int mode,  // an EncMode
                  int prio,
                  const float* __restrict__ act_scale,  // [M, n] (mode 2)
                  const float* __restrict__ act_gain,   // [M, n] (mode 2)
@@ -416,58 +524,49 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
                  const float* __restrict__ x_prev, // [M, B, n] (mode 4)
                  float* __restrict__ x_out,        // [M, B, n] (mode 4)
                  const float* __restrict__ mom) {  // [M] momentum (mode 4)
-  __shared__ float As[2][TBK * BMP];
-  __shared__ float Bs[2][TBK * (TBN + 1)];
+  __shared__ TLds<TBK, BM> As;
+  __shared__ TLds<TBK, TBN> Bs;
 
-  maybe_prio(prio);
-  const int m = blockIdx.z;
-  int tx, ty;
-  tile_coords(tx, ty);
-  const int row0 = ty * BM;
-  const int col0 = tx * TBN;
+  constexpr int NACC = Tile<TBN>::NACC;
+  Tile<TBN> t(prio);
+  const int m = t.m;
   const float* W = Wenc + (long)m * n * d;
   const float* x_m = x + (long)m * x_mstride;
   const float* inv = inv_norms ? inv_norms + (long)m * n : nullptr;
   const bool scaled = inv != nullptr;
 
-  constexpr int NACC = TBN / 64;
-  f32x16 acc[NACC];
-  zero_acc<NACC>(acc);
-  TStage<TBK> sa;
+  TStage<TBK, BM> sa;
   TStage<TBK, TBN> sb;
-
-#define ENC_LA(K) stage_T_load<TBK, BM, ALIGNED>(x_m, d, row0, (K), B, d, nullptr, sa)
-#define ENC_LB(K) stage_T_load<TBK, TBN, ALIGNED>(W, d, col0, (K), n, d, inv, sb)
-#define ENC_WA(BUF) stage_T_write<TBK>(sa, &As[BUF][0], false)
-#define ENC_WB(BUF) stage_T_write<TBK, TBN>(sb, &Bs[BUF][0], scaled)
-  PREFETCH_LOOP(TBK, d, ENC_LA, ENC_LB, ENC_WA, ENC_WB, BMP, TBN + 1)
-#undef ENC_LA
-#undef ENC_LB
-#undef ENC_WA
-#undef ENC_WB
+  gemm_mainloop<TBK>(
+      d, As, Bs, t.acc,
+      [&](int k0) { stage_T_load<TBK, BM, ALIGNED>(x_m, d, t.row0, k0, B, d, nullptr, sa); },
+      [&](int k0) { stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, k0, n, d, inv, sb); },
+      [&](int buf) { stage_T_write(sa, As, buf, false); },
+      [&](int buf) { stage_T_write(sb, Bs, buf, scaled); });
 
   const EpiGeom g = epi_geom<NACC>();
-  EpiIndex<ALIGNED> ei(row0, col0, n, g);
+  EpiIndex<ALIGNED> ei(t.row0, t.col0, n, g);
   float* c_m = c_out + (long)m * B * n;
   const float* bias_m = bias + (long)m * n;
   float* fired_m = fired + (long)m * n;
 
   float l1_sum = 0.f;
-#pragma unroll
-  for (int tj = 0; tj < NACC; ++tj) {
+  epi_cols<NACC, ALIGNED>(g, t.col0, n, [&](int tj, int col, bool col_ok) {
 #pragma clang fp contract(off)
-    int col = col0 + g.wc + tj * 32 + g.l31;
-    bool col_ok = ALIGNED || col < n;
-    if (mode == 1) {
+    const f32x16& acc = t.acc[tj];
+    auto rows = [&](auto per_elem) {
+      epi_rows<ALIGNED>(g, ei, t.row0, B, tj, col, col_ok, per_elem);
+    };
+    // fired[m, col] += the wave's count of active rows in this column
+    auto add_fired = [&](float fired_cnt) {
+      float tot;
+      if (col_ok && halfwave_pair_sum(g, fired_cnt, tot) && tot > 0.f)
+        atomicAdd(&fired_m[col], tot);
+    };
+    if (mode == ENC_RAW) {
       // raw scores for TopK selection: no bias, no relu, no side outputs
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int row = row0 + g.wr + acc_row(r, g.lane);
-        if ((ALIGNED || row < B) && col_ok) ei.ref(c_m, row, col, r, tj) = acc[tj][r];
-      }
-      continue;
-    }
-    if (mode == 2) {
+      rows([&](int r, auto at) { at(c_m) = acc[r]; });
+    } else if (mode == ENC_GATE) {
       // thresholding SAE: code = g((c+gain)/max(a^2,eps)) * a^2; u kept for
       // the backward's gate derivative (k_gc_thresh_t)
       float a = col_ok ? act_scale[(long)m * n + col] : 1.f;
@@ -476,31 +575,21 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
       float s_inv = 1.0f / fmaxf(s_raw, GATE_EPS);
       float* u_m = u_out + (long)m * B * n;
       float fired_cnt = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int row = row0 + g.wr + acc_row(r, g.lane);
-        if ((ALIGNED || row < B) && col_ok) {
-          float av = acc[tj][r];
-          // unguarded, the 16 gate chains of a column would be vectorised
-          // side by side, past the 64 registers of 8 waves/SIMD; an opaque
-          // accumulator value keeps them one after the other
-          if constexpr (ALIGNED) asm volatile("" : "+v"(av));
-          float u = (av + gn) * s_inv;
-          float code = gate_g_scaled(av + gn, s_inv) * s_raw;
-          ei.ref(c_m, row, col, r, tj) = code;
-          ei.ref(u_m, row, col, r, tj) = u;
-          l1_sum += code;
-          fired_cnt += (code > 0.f) ? 1.f : 0.f;
-        }
-      }
-      if (col_ok) {
-        float other = __shfl_xor(fired_cnt, 32, WAVE);
-        float tot = fired_cnt + other;
-        if (g.lane < 32 && tot > 0.f) atomicAdd(&fired_m[col], tot);
-      }
-      continue;
-    }
-    if (mode == 4 || mode == 5) {
+      rows([&](int r, auto at) {
+        float av = acc[r];
+        // unguarded, the 16 gate chains of a column would be vectorised
+        // side by side, past the 64 registers of 8 waves/SIMD; an opaque
+        // accumulator value keeps them one after the other
+        if constexpr (ALIGNED) asm volatile("" : "+v"(av));
+        float u = (av + gn) * s_inv;
+        float code = gate_g_scaled(av + gn, s_inv) * s_raw;
+        at(c_m) = code;
+        at(u_m) = u;
+        l1_sum += code;
+        fired_cnt += (code > 0.f) ? 1.f : 0.f;
+      });
+      add_fired(fired_cnt);
+    } else if (mode == ENC_LISTA_FWD || mode == ENC_LISTA_BWD) {
       // LISTA layer epilogues (HipLISTAStep): the GEMM result `acc` is
       //   mode 4:  s = neg_e W_l^T;  r = y - s;  x = shrink(r, theta);
       //            y' = x + m (x - x_prev)   -> u_out=r, x_out=x, c_out=y'
@@ -510,77 +599,54 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
       const float* xp_m = nullptr;
       float* xo_m = nullptr;
       float* u_m = nullptr;
-      if (mode == 4) {
+      if (mode == ENC_LISTA_FWD) {
         th = col_ok ? act_scale[(long)m * n + col] : 0.f;
         mm = mom[m];
         xp_m = x_prev + (long)m * (long)B * n;
         xo_m = x_out + (long)m * (long)B * n;
         u_m = u_out + (long)m * (long)B * n;
       }
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int row = row0 + g.wr + acc_row(r, g.lane);
-        if ((ALIGNED || row < B) && col_ok) {
-          auto at = [&](auto* p) -> auto& { return ei.ref(p, row, col, r, tj); };
-          float v = at(y_m) - acc[tj][r];
-          if (mode == 5) {
-            at(c_m) = v;
-          } else {
-            at(u_m) = v;  // r_l, kept for the backward's shrink mask
-            float a = fabsf(v) - th;
-            float xa = (a > 0.f) ? ((v > 0.f) ? a : -a) : 0.f;
-            at(xo_m) = xa;
-            at(c_m) = fmaf(mm, xa - at(xp_m), xa);
-          }
+      rows([&](int r, auto at) {
+        float v = at(y_m) - acc[r];
+        if (mode == ENC_LISTA_BWD) {
+          at(c_m) = v;
+        } else {
+          at(u_m) = v;  // r_l, kept for the backward's shrink mask
+          float a = fabsf(v) - th;
+          float xa = (a > 0.f) ? ((v > 0.f) ? a : -a) : 0.f;
+          at(xo_m) = xa;
+          at(c_m) = fmaf(mm, xa - at(xp_m), xa);
         }
-      }
-      continue;
-    }
-    if (mode == 3) {
+      });
+    } else if (mode == ENC_REVERSE) {
       // reverse SAE (sae_ensemble.py:447-503): code = pre * [pre + b > 0]
       // (the bias is removed from active features before decoding, so the
       // code can be negative and the L1 partial needs |code|)
       float bj = col_ok ? bias_m[col] : 0.f;
       float fired_cnt = 0.f;
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int row = row0 + g.wr + acc_row(r, g.lane);
-        if ((ALIGNED || row < B) && col_ok) {
-          float pre = acc[tj][r];
-          float v = (pre + bj > 0.f) ? pre : 0.f;
-          ei.ref(c_m, row, col, r, tj) = v;
-          l1_sum += fabsf(v);
-          fired_cnt += (v != 0.f) ? 1.f : 0.f;
-        }
-      }
-      if (col_ok) {
-        float other = __shfl_xor(fired_cnt, 32, WAVE);
-        float tot = fired_cnt + other;
-        if (g.lane < 32 && tot > 0.f) atomicAdd(&fired_m[col], tot);
-      }
-      continue;
-    }
-    float bj = col_ok ? bias_m[col] : 0.f;
-    // coefficient mask (reference K9): columns >= dict_sizes[m] are dead
-    bool live = col_ok && (!dict_sizes || col < dict_sizes[m]);
-    float fired_cnt = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int row = row0 + g.wr + acc_row(r, g.lane);
-      if ((ALIGNED || row < B) && col_ok) {
-        float v = live ? fmaxf(acc[tj][r] + bj, 0.f) : 0.f;
-        ei.ref(c_m, row, col, r, tj) = v;
+      rows([&](int r, auto at) {
+        float pre = acc[r];
+        float v = (pre + bj > 0.f) ? pre : 0.f;
+        at(c_m) = v;
+        l1_sum += fabsf(v);
+        fired_cnt += (v != 0.f) ? 1.f : 0.f;
+      });
+      add_fired(fired_cnt);
+    } else {  // ENC_RELU
+      float bj = col_ok ? bias_m[col] : 0.f;
+      // coefficient mask (reference K9): columns >= dict_sizes[m] are dead
+      bool live = col_ok && (!dict_sizes || col < dict_sizes[m]);
+      float fired_cnt = 0.f;
+      rows([&](int r, auto at) {
+        float v = live ? fmaxf(acc[r] + bj, 0.f) : 0.f;
+        at(c_m) = v;
         l1_sum += v;
         fired_cnt += (v > 0.f) ? 1.f : 0.f;
-      }
+      });
+      add_fired(fired_cnt);
     }
-    if (col_ok) {
-      float other = __shfl_xor(fired_cnt, 32, WAVE);
-      float tot = fired_cnt + other;
-      if (g.lane < 32 && tot > 0.f) atomicAdd(&fired_m[col], tot);
-    }
-  }
-  if (mode == 0 || mode == 2 || mode == 3) {
+  });
+  if (mode == ENC_RELU || mode == ENC_GATE || mode == ENC_REVERSE) {
     l1_sum = wave_reduce_sum(l1_sum);
     if (g.lane == 0) atomicAdd(&loss_parts[m * 2 + 1], l1_sum);
   }
@@ -599,56 +665,39 @@ void k_dec_fwd_t(const float* __restrict__ c,       // [M, B, n]
                  float* __restrict__ loss_parts,    // [M, 2]
                  int B, int d, int n, int prio,
                  long x_mstride) {  // 0: shared [B,d]; else [M,B,d]
-  __shared__ float As[2][TBK * BMP];
-  __shared__ float Bs[2][TBK * TBN];
+  __shared__ TLds<TBK, BM> As;
+  __shared__ DLds<TBK, TBN> Bs;
 
-  maybe_prio(prio);
-  const int m = blockIdx.z;
-  int tx, ty;
-  tile_coords(tx, ty);
-  const int row0 = ty * BM;
-  const int col0 = tx * TBN;
+  constexpr int NACC = Tile<TBN>::NACC;
+  Tile<TBN> t(prio);
+  const int m = t.m;
   const float* c_m = c + (long)m * B * n;
   const float* W = Wdec + (long)m * n * d;
   const float* x_m = x + (long)m * x_mstride;
   const float* inv = inv_norms + (long)m * n;
 
-  constexpr int NACC = TBN / 64;
-  f32x16 acc[NACC];
-  zero_acc<NACC>(acc);
-  TStage<TBK> sa;
+  TStage<TBK, BM> sa;
   DStage<TBK, TBN> sb;
-
-#define DEC_LA(K) stage_T_load<TBK, BM, ALIGNED>(c_m, n, row0, (K), B, n, nullptr, sa)
-#define DEC_LB(K) stage_D_load<TBK, TBN, ALIGNED>(W, d, (K), col0, n, d, inv, sb)
-#define DEC_WA(BUF) stage_T_write<TBK>(sa, &As[BUF][0], false)
-#define DEC_WB(BUF) stage_D_write<TBK, TBN>(sb, &Bs[BUF][0], true)
-  PREFETCH_LOOP(TBK, n, DEC_LA, DEC_LB, DEC_WA, DEC_WB, BMP, TBN)
-#undef DEC_LA
-#undef DEC_LB
-#undef DEC_WA
-#undef DEC_WB
+  gemm_mainloop<TBK>(
+      n, As, Bs, t.acc,
+      [&](int k0) { stage_T_load<TBK, BM, ALIGNED>(c_m, n, t.row0, k0, B, n, nullptr, sa); },
+      [&](int k0) { stage_D_load<TBK, TBN, ALIGNED>(W, d, k0, t.col0, n, d, inv, sb); },
+      [&](int buf) { stage_T_write(sa, As, buf, false); },
+      [&](int buf) { stage_D_write(sb, Bs, buf, true); });
 
   const EpiGeom g = epi_geom<NACC>();
-  EpiIndex<ALIGNED> ei(row0, col0, d, g);
+  EpiIndex<ALIGNED> ei(t.row0, t.col0, d, g);
   float* r_m = r_out + (long)m * B * d;
 
   float mse_sum = 0.f;
-#pragma unroll
-  for (int tj = 0; tj < NACC; ++tj) {
+  epi_cols<NACC, ALIGNED>(g, t.col0, d, [&](int tj, int col, bool col_ok) {
 #pragma clang fp contract(off)
-    int col = col0 + g.wc + tj * 32 + g.l31;
-    bool col_ok = ALIGNED || col < d;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int row = row0 + g.wr + acc_row(r, g.lane);
-      if ((ALIGNED || row < B) && col_ok) {
-        float rv = acc[tj][r] - ei.ref(x_m, row, col, r, tj);
-        ei.ref(r_m, row, col, r, tj) = rv;
-        mse_sum = fmaf(rv, rv, mse_sum);
-      }
-    }
-  }
+    epi_rows<ALIGNED>(g, ei, t.row0, B, tj, col, col_ok, [&](int r, auto at) {
+      float rv = t.acc[tj][r] - at(x_m);
+      at(r_m) = rv;
+      mse_sum = fmaf(rv, rv, mse_sum);
+    });
+  });
   mse_sum = wave_reduce_sum(mse_sum);
   if (g.lane == 0) atomicAdd(&loss_parts[m * 2 + 0], mse_sum);
 }
@@ -666,15 +715,12 @@ void k_gc_t(const float* __restrict__ r,        // [M, B, d]
             float* __restrict__ gpre_out,       // [M, B, n]
             float* __restrict__ gb_part,        // [M, nrg, n] per-32-row column sums
             int B, int d, int n, int prio, int gc_mode) {
-  __shared__ float As[2][TBK * BMP];
-  __shared__ float Bs[2][TBK * (TBN + 1)];
+  __shared__ TLds<TBK, BM> As;
+  __shared__ TLds<TBK, TBN> Bs;
 
-  maybe_prio(prio);
-  const int m = blockIdx.z;
-  int tx, ty;
-  tile_coords(tx, ty);
-  const int row0 = ty * BM;
-  const int col0 = tx * TBN;
+  constexpr int NACC = Tile<TBN>::NACC;
+  Tile<TBN> t(prio);
+  const int m = t.m;
   const float* r_m = r + (long)m * B * d;
   const float* W = Wdec + (long)m * n * d;
   const float* inv = inv_norms + (long)m * n;
@@ -682,61 +728,71 @@ void k_gc_t(const float* __restrict__ r,        // [M, B, d]
   const float gscale = 2.0f / ((float)B * (float)d);
   const float l1_term = l1_alpha[m] / (float)B;
 
-  constexpr int NACC = TBN / 64;
-  f32x16 acc[NACC];
-  zero_acc<NACC>(acc);
-  TStage<TBK> sa;
+  TStage<TBK, BM> sa;
   TStage<TBK, TBN> sb;
-
-#define GC_LA(K) stage_T_load<TBK, BM, ALIGNED>(r_m, d, row0, (K), B, d, nullptr, sa)
-#define GC_LB(K) stage_T_load<TBK, TBN, ALIGNED>(W, d, col0, (K), n, d, inv, sb)
-#define GC_WA(BUF) stage_T_write<TBK>(sa, &As[BUF][0], false)
-#define GC_WB(BUF) stage_T_write<TBK, TBN>(sb, &Bs[BUF][0], true)
-  PREFETCH_LOOP(TBK, d, GC_LA, GC_LB, GC_WA, GC_WB, BMP, TBN + 1)
-#undef GC_LA
-#undef GC_LB
-#undef GC_WA
-#undef GC_WB
+  // This kernel alone writes gemm_mainloop's loop and the epilogue walk out.
+  // Through the helpers its aligned <16, 8, 128> variant is scheduled
+  // differently (and with epi_cols/epi_rows takes 64 VGPRs, not 63) and
+  // measured 0.4-0.7% slower; written out it compiles to the instruction
+  // stream it had before the helpers existed (profiles/README.md, r04).
+  {
+    constexpr int ASTR = TLds<TBK, BM>::STRIDE, BSTR = TLds<TBK, TBN>::STRIDE;
+    int cur = 0;
+    stage_T_load<TBK, BM, ALIGNED>(r_m, d, t.row0, 0, B, d, nullptr, sa);
+    stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, 0, n, d, inv, sb);
+    stage_T_write(sa, As, 0, false);
+    stage_T_write(sb, Bs, 0, true);
+    __syncthreads();
+    for (int k0 = TBK; k0 < d; k0 += TBK) {
+      stage_T_load<TBK, BM, ALIGNED>(r_m, d, t.row0, k0, B, d, nullptr, sa);
+      stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, k0, n, d, inv, sb);
+      mfma_tile<TBK, NACC, ASTR, BSTR>(As.buf[cur], Bs.buf[cur], t.acc);
+      stage_T_write(sa, As, cur ^ 1, false);
+      stage_T_write(sb, Bs, cur ^ 1, true);
+      __syncthreads();
+      cur ^= 1;
+    }
+    mfma_tile<TBK, NACC, ASTR, BSTR>(As.buf[cur], Bs.buf[cur], t.acc);
+  }
 
   const EpiGeom g = epi_geom<NACC>();
-  EpiIndex<ALIGNED> ei(row0, col0, n, g);
+  EpiIndex<ALIGNED> ei(t.row0, t.col0, n, g);
   float* g_m = gpre_out + (long)m * B * n;
   // bias grad: each wave owns one 32-row group of its columns and stores that
   // group's column sum with a plain store; k_colsum_groups adds the groups in
   // a fixed order (bitwise reproducible, unlike float atomics across blocks)
   const int nrg = (B + 31) / 32;
-  const int rg = (row0 + g.wr) / 32;
+  const int rg = (t.row0 + g.wr) / 32;
   float* gb_m = gb_part + ((long)m * nrg + rg) * n;
 
+  // the walk of epi_cols/epi_rows, written out (see above)
 #pragma unroll
   for (int tj = 0; tj < NACC; ++tj) {
 #pragma clang fp contract(off)
-    int col = col0 + g.wc + tj * 32 + g.l31;
+    int col = t.col0 + g.wc + tj * 32 + g.l31;
     bool col_ok = ALIGNED || col < n;
     float colsum = 0.f;
 #pragma unroll
     for (int r_ = 0; r_ < 16; ++r_) {
-      int row = row0 + g.wr + acc_row(r_, g.lane);
+      int row = t.row0 + g.wr + acc_row(r_, g.lane);
       if ((ALIGNED || row < B) && col_ok) {
         float cv = ei.ref(c_m, row, col, r_, tj);
         float gv;
-        if (gc_mode == 1) {
+        if (gc_mode == GC_REVERSE) {
           // reverse SAE: active set is cv != 0, l1 grad is sign(cv), and
           // the bias receives no gradient from the code path
           float sgn = (cv > 0.f) ? 1.f : ((cv < 0.f) ? -1.f : 0.f);
-          gv = (cv != 0.f) ? (gscale * acc[tj][r_] + l1_term * sgn) : 0.f;
+          gv = (cv != 0.f) ? (gscale * t.acc[tj][r_] + l1_term * sgn) : 0.f;
         } else {
-          gv = (cv > 0.f) ? fmaf(gscale, acc[tj][r_], l1_term) : 0.f;
+          gv = (cv > 0.f) ? fmaf(gscale, t.acc[tj][r_], l1_term) : 0.f;
         }
         ei.ref(g_m, row, col, r_, tj) = gv;
         colsum += gv;
       }
     }
-    if (col_ok && gc_mode == 0) {
-      float other = __shfl_xor(colsum, 32, WAVE);
-      float tot = colsum + other;
-      if (g.lane < 32 && (ALIGNED || rg < nrg)) gb_m[col] = tot;
-    }
+    float tot;
+    if (col_ok && gc_mode == GC_RELU && halfwave_pair_sum(g, colsum, tot) && (ALIGNED || rg < nrg))
+      gb_m[col] = tot;
   }
 }
 
@@ -792,15 +848,12 @@ void k_gc_thresh_t(const float* __restrict__ r,        // [M, B, d]
                    float* __restrict__ g_gain,         // [M, n]
                    float* __restrict__ g_scale,        // [M, n]
                    int B, int d, int n, int prio) {
-  __shared__ float As[2][TBK * BMP];
-  __shared__ float Bs[2][TBK * (TBN + 1)];
+  __shared__ TLds<TBK, BM> As;
+  __shared__ TLds<TBK, TBN> Bs;
 
-  maybe_prio(prio);
-  const int m = blockIdx.z;
-  int tx, ty;
-  tile_coords(tx, ty);
-  const int row0 = ty * BM;
-  const int col0 = tx * TBN;
+  constexpr int NACC = Tile<TBN>::NACC;
+  Tile<TBN> t(prio);
+  const int m = t.m;
   const float* r_m = r + (long)m * B * d;
   const float* W = Wdec + (long)m * n * d;
   const float* inv = inv_norms + (long)m * n;
@@ -809,32 +862,28 @@ void k_gc_thresh_t(const float* __restrict__ r,        // [M, B, d]
   const float gscale = 2.0f / ((float)B * (float)d);
   const float l1_term = l1_alpha[m] / (float)B;
 
-  constexpr int NACC = TBN / 64;
-  f32x16 acc[NACC];
-  zero_acc<NACC>(acc);
-  TStage<TBK> sa;
+  TStage<TBK, BM> sa;
   TStage<TBK, TBN> sb;
-
-#define GCT_LA(K) stage_T_load<TBK, BM, ALIGNED>(r_m, d, row0, (K), B, d, nullptr, sa)
-#define GCT_LB(K) stage_T_load<TBK, TBN, ALIGNED>(W, d, col0, (K), n, d, inv, sb)
-#define GCT_WA(BUF) stage_T_write<TBK>(sa, &As[BUF][0], false)
-#define GCT_WB(BUF) stage_T_write<TBK, TBN>(sb, &Bs[BUF][0], true)
-  PREFETCH_LOOP(TBK, d, GCT_LA, GCT_LB, GCT_WA, GCT_WB, BMP, TBN + 1)
-#undef GCT_LA
-#undef GCT_LB
-#undef GCT_WA
-#undef GCT_WB
+  gemm_mainloop<TBK>(
+      d, As, Bs, t.acc,
+      [&](int k0) { stage_T_load<TBK, BM, ALIGNED>(r_m, d, t.row0, k0, B, d, nullptr, sa); },
+      [&](int k0) { stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, k0, n, d, inv, sb); },
+      [&](int buf) { stage_T_write(sa, As, buf, false); },
+      [&](int buf) { stage_T_write(sb, Bs, buf, true); });
 
   const EpiGeom g = epi_geom<NACC>();
-  EpiIndex<ALIGNED> ei(row0, col0, n, g);
+  EpiIndex<ALIGNED> ei(t.row0, t.col0, n, g);
   float* g_m = gpre_out + (long)m * B * n;
   float* gg_m = g_gain + (long)m * n;
   float* gs_m = g_scale + (long)m * n;
 
+  // The traversal is written out here for the same reason as in k_gc_t: with
+  // epi_cols/epi_rows the aligned <16, 8, 128> variant went from 63 to 64
+  // VGPRs and measured about 1% slower (profiles/README.md, r04).
 #pragma unroll
   for (int tj = 0; tj < NACC; ++tj) {
 #pragma clang fp contract(off)
-    int col = col0 + g.wc + tj * 32 + g.l31;
+    int col = t.col0 + g.wc + tj * 32 + g.l31;
     bool col_ok = ALIGNED || col < n;
     float a = col_ok ? act_scale[(long)m * n + col] : 1.f;
     float s_raw = a * a;
@@ -844,13 +893,13 @@ void k_gc_thresh_t(const float* __restrict__ r,        // [M, B, d]
     float gain_colsum = 0.f, scale_colsum = 0.f;
 #pragma unroll
     for (int r_ = 0; r_ < 16; ++r_) {
-      int row = row0 + g.wr + acc_row(r_, g.lane);
+      int row = t.row0 + g.wr + acc_row(r_, g.lane);
       if ((ALIGNED || row < B) && col_ok) {
         auto at = [&](auto* p) -> auto& { return ei.ref(p, row, col, r_, tj); };
         float code = at(c_m);
         float uv = at(u_m);
         float gp = gate_gp(uv);
-        float gv = fmaf(gscale, acc[tj][r_], (code > 0.f) ? l1_term : 0.f);
+        float gv = fmaf(gscale, t.acc[tj][r_], (code > 0.f) ? l1_term : 0.f);
         float gc_ = gv * gp * f;
         at(g_m) = gc_;
         gain_colsum += gc_;
@@ -858,11 +907,12 @@ void k_gc_thresh_t(const float* __restrict__ r,        // [M, B, d]
       }
     }
     if (col_ok) {
-      float og = __shfl_xor(gain_colsum, 32, WAVE);
-      float os = __shfl_xor(scale_colsum, 32, WAVE);
-      if (g.lane < 32) {
-        if (gain_colsum + og != 0.f) atomicAdd(&gg_m[col], gain_colsum + og);
-        if (scale_colsum + os != 0.f) atomicAdd(&gs_m[col], scale_colsum + os);
+      float gain_tot, scale_tot;
+      const bool owner = halfwave_pair_sum(g, gain_colsum, gain_tot);
+      halfwave_pair_sum(g, scale_colsum, scale_tot);
+      if (owner) {
+        if (gain_tot != 0.f) atomicAdd(&gg_m[col], gain_tot);
+        if (scale_tot != 0.f) atomicAdd(&gs_m[col], scale_tot);
       }
     }
   }
@@ -1025,54 +1075,36 @@ void k_grad_w_t(const float* __restrict__ P, long p_batch_stride,
                 float* __restrict__ gw,  // [M, n, d]
                 float alpha, float beta,
                 int B, int n, int d, int prio) {
-  __shared__ float As[2][TBK * BM];
-  __shared__ float Bs[2][TBK * TBN];
+  __shared__ DLds<TBK, BM> As;
+  __shared__ DLds<TBK, TBN> Bs;
 
-  maybe_prio(prio);
-  const int m = blockIdx.z;
-  int tx, ty;
-  tile_coords(tx, ty);
-  const int row0 = ty * BM;  // n rows
-  const int col0 = tx * TBN;  // d cols
+  constexpr int NACC = Tile<TBN>::NACC;
+  Tile<TBN> t(prio);  // row0: n rows, col0: d cols
+  const int m = t.m;
   const float* P_m = P + (long)m * p_batch_stride;
   const float* Q_m = Q + (long)m * q_batch_stride;
 
-  constexpr int NACC = TBN / 64;
-  f32x16 acc[NACC];
-  zero_acc<NACC>(acc);
-  DStage<TBK> sa;
+  DStage<TBK, BM> sa;
   DStage<TBK, TBN> sb;
-
-#define GW_LA(K) stage_D_load<TBK, BM, ALIGNED>(P_m, n, (K), row0, B, n, nullptr, sa)
-#define GW_LB(K) stage_D_load<TBK, TBN, ALIGNED>(Q_m, d, (K), col0, B, d, nullptr, sb)
-#define GW_WA(BUF) stage_D_write<TBK>(sa, &As[BUF][0], false)
-#define GW_WB(BUF) stage_D_write<TBK, TBN>(sb, &Bs[BUF][0], false)
-  PREFETCH_LOOP(TBK, B, GW_LA, GW_LB, GW_WA, GW_WB, BM, TBN)
-#undef GW_LA
-#undef GW_LB
-#undef GW_WA
-#undef GW_WB
+  gemm_mainloop<TBK>(
+      B, As, Bs, t.acc,
+      [&](int k0) { stage_D_load<TBK, BM, ALIGNED>(P_m, n, k0, t.row0, B, n, nullptr, sa); },
+      [&](int k0) { stage_D_load<TBK, TBN, ALIGNED>(Q_m, d, k0, t.col0, B, d, nullptr, sb); },
+      [&](int buf) { stage_D_write(sa, As, buf, false); },
+      [&](int buf) { stage_D_write(sb, Bs, buf, false); });
 
   const EpiGeom g = epi_geom<NACC>();
-  EpiIndex<ALIGNED> ei(row0, col0, d, g);
+  EpiIndex<ALIGNED> ei(t.row0, t.col0, d, g);
   float* gw_m = gw + (long)m * n * d;
 
-#pragma unroll
-  for (int tj = 0; tj < NACC; ++tj) {
+  epi_cols<NACC, ALIGNED>(g, t.col0, d, [&](int tj, int col, bool col_ok) {
 #pragma clang fp contract(off)
-    int col = col0 + g.wc + tj * 32 + g.l31;
-    bool col_ok = ALIGNED || col < d;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int row = row0 + g.wr + acc_row(r, g.lane);
-      if ((ALIGNED || row < n) && col_ok) {
-        auto at = [&](auto* p) -> auto& { return ei.ref(p, row, col, r, tj); };
-        float v = alpha * acc[tj][r];
-        if (beta != 0.f) v = fmaf(beta, at(gw_m), v);
-        at(gw_m) = v;
-      }
-    }
-  }
+    epi_rows<ALIGNED>(g, ei, t.row0, n, tj, col, col_ok, [&](int r, auto at) {
+      float v = alpha * t.acc[tj][r];
+      if (beta != 0.f) v = fmaf(beta, at(gw_m), v);
+      at(gw_m) = v;
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1365,71 +1397,49 @@ void k_enc_fwd2_t(const float* __restrict__ xT,      // [d, B]
                   float* __restrict__ fired,         // [M, n]
                   int B, int d, int n, int mode, int prio,
                   const int* __restrict__ dict_sizes) {
-  __shared__ float As[2][TBK * BM];
-  __shared__ float Bs[2][TBK * TBN];
+  __shared__ DLds<TBK, BM> As;
+  __shared__ DLds<TBK, TBN> Bs;
 
-  maybe_prio(prio);
-  const int m = blockIdx.z;
-  int tx, ty;
-  tile_coords(tx, ty);
-  const int row0 = ty * BM;   // batch rows
-  const int col0 = tx * TBN;   // dict cols
+  constexpr int NACC = Tile<TBN>::NACC;
+  Tile<TBN> t(prio);  // row0: batch rows, col0: dict cols
+  const int m = t.m;
   const float* WT_m = WT + (long)m * d * n;
 
-  constexpr int NACC = TBN / 64;
-  f32x16 acc[NACC];
-  zero_acc<NACC>(acc);
-  DStage<TBK> sa;
+  DStage<TBK, BM> sa;
   DStage<TBK, TBN> sb;
-
-#define ENC2_LA(K) stage_D_load<TBK>(xT, B, (K), row0, d, B, nullptr, sa)
-#define ENC2_LB(K) stage_D_load<TBK, TBN>(WT_m, n, (K), col0, d, n, nullptr, sb)
-#define ENC2_WA(BUF) stage_D_write<TBK>(sa, &As[BUF][0], false)
-#define ENC2_WB(BUF) stage_D_write<TBK, TBN>(sb, &Bs[BUF][0], false)
-  PREFETCH_LOOP(TBK, d, ENC2_LA, ENC2_LB, ENC2_WA, ENC2_WB, BM, TBN)
-#undef ENC2_LA
-#undef ENC2_LB
-#undef ENC2_WA
-#undef ENC2_WB
+  gemm_mainloop<TBK>(
+      d, As, Bs, t.acc,
+      [&](int k0) { stage_D_load<TBK, BM>(xT, B, k0, t.row0, d, B, nullptr, sa); },
+      [&](int k0) { stage_D_load<TBK, TBN>(WT_m, n, k0, t.col0, d, n, nullptr, sb); },
+      [&](int buf) { stage_D_write(sa, As, buf, false); },
+      [&](int buf) { stage_D_write(sb, Bs, buf, false); });
 
   const EpiGeom g = epi_geom<NACC>();
+  EpiIndex<false> ei(t.row0, t.col0, n, g);
   float* c_m = c_out + (long)m * B * n;
   const float* bias_m = bias + (long)m * n;
   float* fired_m = fired + (long)m * n;
 
   float l1_sum = 0.f;
-#pragma unroll
-  for (int tj = 0; tj < NACC; ++tj) {
-    int col = col0 + g.wc + tj * 32 + g.l31;
-    bool col_ok = col < n;
-    if (mode == 1) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int row = row0 + g.wr + acc_row(r, g.lane);
-        if (row < B && col_ok) c_m[(long)row * n + col] = acc[tj][r];
-      }
-      continue;
+  epi_cols<NACC, false>(g, t.col0, n, [&](int tj, int col, bool col_ok) {
+    if (mode == ENC_RAW) {
+      epi_rows<false>(g, ei, t.row0, B, tj, col, col_ok,
+                      [&](int r, auto at) { at(c_m) = t.acc[tj][r]; });
+      return;
     }
     float bj = col_ok ? bias_m[col] : 0.f;
     bool live = col_ok && (!dict_sizes || col < dict_sizes[m]);
     float fired_cnt = 0.f;
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-      int row = row0 + g.wr + acc_row(r, g.lane);
-      if (row < B && col_ok) {
-        float v = live ? fmaxf(acc[tj][r] + bj, 0.f) : 0.f;
-        c_m[(long)row * n + col] = v;
-        l1_sum += v;
-        fired_cnt += (v > 0.f) ? 1.f : 0.f;
-      }
-    }
-    if (col_ok) {
-      float other = __shfl_xor(fired_cnt, 32, WAVE);
-      float tot = fired_cnt + other;
-      if (g.lane < 32 && tot > 0.f) atomicAdd(&fired_m[col], tot);
-    }
-  }
-  if (mode == 0) {
+    epi_rows<false>(g, ei, t.row0, B, tj, col, col_ok, [&](int r, auto at) {
+      float v = live ? fmaxf(t.acc[tj][r] + bj, 0.f) : 0.f;
+      at(c_m) = v;
+      l1_sum += v;
+      fired_cnt += (v > 0.f) ? 1.f : 0.f;
+    });
+    float tot;
+    if (col_ok && halfwave_pair_sum(g, fired_cnt, tot) && tot > 0.f) atomicAdd(&fired_m[col], tot);
+  });
+  if (mode == ENC_RELU) {
     l1_sum = wave_reduce_sum(l1_sum);
     if (g.lane == 0) atomicAdd(&loss_parts[m * 2 + 1], l1_sum);
   }
@@ -1447,66 +1457,49 @@ void k_gc2_t(const float* __restrict__ rT,       // [M, d, B]
              float* __restrict__ gpre_out,       // [M, B, n]
              float* __restrict__ g_bias,         // [M, n]
              int B, int d, int n, int prio, int gc_mode) {
-  __shared__ float As[2][TBK * BM];
-  __shared__ float Bs[2][TBK * TBN];
+  __shared__ DLds<TBK, BM> As;
+  __shared__ DLds<TBK, TBN> Bs;
 
-  maybe_prio(prio);
-  const int m = blockIdx.z;
-  int tx, ty;
-  tile_coords(tx, ty);
-  const int row0 = ty * BM;
-  const int col0 = tx * TBN;
+  constexpr int NACC = Tile<TBN>::NACC;
+  Tile<TBN> t(prio);
+  const int m = t.m;
   const float* rT_m = rT + (long)m * d * B;
   const float* WT_m = WT + (long)m * d * n;
   const float* c_m = c + (long)m * B * n;
   const float gscale = 2.0f / ((float)B * (float)d);
   const float l1_term = l1_alpha[m] / (float)B;
 
-  constexpr int NACC = TBN / 64;
-  f32x16 acc[NACC];
-  zero_acc<NACC>(acc);
-  DStage<TBK> sa;
+  DStage<TBK, BM> sa;
   DStage<TBK, TBN> sb;
-
-#define GC2_LA(K) stage_D_load<TBK>(rT_m, B, (K), row0, d, B, nullptr, sa)
-#define GC2_LB(K) stage_D_load<TBK, TBN>(WT_m, n, (K), col0, d, n, nullptr, sb)
-#define GC2_WA(BUF) stage_D_write<TBK>(sa, &As[BUF][0], false)
-#define GC2_WB(BUF) stage_D_write<TBK, TBN>(sb, &Bs[BUF][0], false)
-  PREFETCH_LOOP(TBK, d, GC2_LA, GC2_LB, GC2_WA, GC2_WB, BM, TBN)
-#undef GC2_LA
-#undef GC2_LB
-#undef GC2_WA
-#undef GC2_WB
+  gemm_mainloop<TBK>(
+      d, As, Bs, t.acc,
+      [&](int k0) { stage_D_load<TBK, BM>(rT_m, B, k0, t.row0, d, B, nullptr, sa); },
+      [&](int k0) { stage_D_load<TBK, TBN>(WT_m, n, k0, t.col0, d, n, nullptr, sb); },
+      [&](int buf) { stage_D_write(sa, As, buf, false); },
+      [&](int buf) { stage_D_write(sb, Bs, buf, false); });
 
   const EpiGeom g = epi_geom<NACC>();
+  EpiIndex<false> ei(t.row0, t.col0, n, g);
   float* g_m = gpre_out + (long)m * B * n;
   float* gb_m = g_bias + (long)m * n;
 
-#pragma unroll
-  for (int tj = 0; tj < NACC; ++tj) {
-    int col = col0 + g.wc + tj * 32 + g.l31;
-    bool col_ok = col < n;
+  // default floating-point contraction here, unlike k_gc_t
+  epi_cols<NACC, false>(g, t.col0, n, [&](int tj, int col, bool col_ok) {
     float colsum = 0.f;
-#pragma unroll
-    for (int r_ = 0; r_ < 16; ++r_) {
-      int row = row0 + g.wr + acc_row(r_, g.lane);
-      if (row < B && col_ok) {
-        float cv = c_m[(long)row * n + col];
-        float gv;
-        if (gc_mode == 1) {
-          float sgn = (cv > 0.f) ? 1.f : ((cv < 0.f) ? -1.f : 0.f);
-          gv = (cv != 0.f) ? (gscale * acc[tj][r_] + l1_term * sgn) : 0.f;
-        } else {
-          gv = (cv > 0.f) ? (gscale * acc[tj][r_] + l1_term) : 0.f;
-        }
-        g_m[(long)row * n + col] = gv;
-        colsum += gv;
+    epi_rows<false>(g, ei, t.row0, B, tj, col, col_ok, [&](int r_, auto at) {
+      float cv = at(c_m);
+      float gv;
+      if (gc_mode == GC_REVERSE) {
+        float sgn = (cv > 0.f) ? 1.f : ((cv < 0.f) ? -1.f : 0.f);
+        gv = (cv != 0.f) ? (gscale * t.acc[tj][r_] + l1_term * sgn) : 0.f;
+      } else {
+        gv = (cv > 0.f) ? (gscale * t.acc[tj][r_] + l1_term) : 0.f;
       }
-    }
-    if (col_ok && gc_mode == 0) {
-      float other = __shfl_xor(colsum, 32, WAVE);
-      float tot = colsum + other;
-      if (g.lane < 32 && tot != 0.f) atomicAdd(&gb_m[col], tot);
-    }
-  }
+      at(g_m) = gv;
+      colsum += gv;
+    });
+    float tot;
+    if (col_ok && gc_mode == GC_RELU && halfwave_pair_sum(g, colsum, tot) && tot != 0.f)
+      atomicAdd(&gb_m[col], tot);
+  });
 }

@@ -7,16 +7,42 @@
 
 #include "sae_kernels.hip"
 
-#define CHECK_IN(t)                                           \
-  TORCH_CHECK(t.is_cuda(), #t " must be on GPU");             \
-  TORCH_CHECK(t.is_contiguous(), #t " must be contiguous");   \
-  TORCH_CHECK(t.scalar_type() == torch::kFloat32, #t " must be fp32");
+static inline void check_in(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat32, name, " must be fp32");
+}
+#define CHECK_IN(t) check_in(t, #t)
+
+// optional fp32 tensor -> checked pointer, nullptr when absent
+static inline float* opt_ptr(const c10::optional<torch::Tensor>& t, const char* name) {
+  if (!t.has_value()) return nullptr;
+  check_in(*t, name);
+  return t->data_ptr<float>();
+}
+#define OPT_PTR(t) opt_ptr(t, #t)
+
+static inline int* int32_ptr(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.is_contiguous() && t.scalar_type() == torch::kInt32,
+              name, " must be int32 GPU");
+  return t.data_ptr<int>();
+}
 
 static inline hipStream_t cur_stream() {
   return at::hip::getCurrentHIPStream().stream();
 }
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
+
+// output-tile width LAUNCH_TILE_BN takes for a requested bn
+static inline int tile_bn(int64_t bn) { return bn == 256 ? 256 : BN; }
+
+// batch stride of x between models: 0 for a shared [B, d], B*d for [M, B, d]
+static inline long x_model_stride(const torch::Tensor& x, int M) {
+  if (x.dim() != 3) return 0;
+  TORCH_CHECK(x.size(0) == M, "per-model x must be [M,B,d]");
+  return (long)x.size(1) * x.size(2);
+}
 
 // Tile dispatch for the GEMM launchers, stated once.  The kernels are
 // instantiated as <TBK, MINW, TBN, ALIGNED>: TBK 16 and 32 are the two depths
@@ -109,61 +135,26 @@ void enc_fwd(torch::Tensor x, torch::Tensor Wenc, torch::Tensor bias,
   CHECK_IN(x); CHECK_IN(Wenc); CHECK_IN(bias); CHECK_IN(c_out);
   CHECK_IN(loss_parts); CHECK_IN(fired);
   int M = Wenc.size(0), n = Wenc.size(1), d = Wenc.size(2);
-  long x_mstride = 0;
-  if (x.dim() == 3) {
-    TORCH_CHECK(x.size(0) == M, "per-model x must be [M,B,d]");
-    x_mstride = (long)x.size(1) * x.size(2);
-  }
+  const long x_mstride = x_model_stride(x, M);
   int B = x.size(x.dim() - 2);
   TORCH_CHECK(d % 4 == 0 && n % 4 == 0, "d and n must be multiples of 4 (float4 staging)");
-  const float* inv = nullptr;
-  if (inv_norms.has_value()) {
-    CHECK_IN(inv_norms.value());
-    inv = inv_norms->data_ptr<float>();
-  }
-  const float* a_p = nullptr;
-  const float* gn_p = nullptr;
-  float* u_p = nullptr;
-  if (mode == 2) {
+  // which epilogue reads which optional operand; the others may be absent
+  if (mode == ENC_GATE)
     TORCH_CHECK(act_scale && act_gain && u_out, "mode 2 needs act_scale/act_gain/u_out");
-    CHECK_IN(act_scale.value()); CHECK_IN(act_gain.value()); CHECK_IN(u_out.value());
-    a_p = act_scale->data_ptr<float>();
-    gn_p = act_gain->data_ptr<float>();
-    u_p = u_out->data_ptr<float>();
-  }
-  const int* ds_p = nullptr;
-  if (dict_sizes.has_value()) {
-    TORCH_CHECK(dict_sizes->is_cuda() && dict_sizes->is_contiguous() &&
-                dict_sizes->scalar_type() == torch::kInt32, "dict_sizes must be int32 GPU");
-    ds_p = dict_sizes->data_ptr<int>();
-  }
-  const float* yin_p = nullptr;
-  const float* xp_p = nullptr;
-  float* xo_p = nullptr;
-  const float* mom_p = nullptr;
-  if (mode == 4 || mode == 5) {
-    TORCH_CHECK(y_in, "modes 4/5 need y_in");
-    CHECK_IN(y_in.value());
-    yin_p = y_in->data_ptr<float>();
-    if (mode == 4) {
-      TORCH_CHECK(x_prev && x_out && mom && act_scale, "mode 4 needs x_prev/x_out/mom/act_scale(theta)/u_out");
-      CHECK_IN(x_prev.value()); CHECK_IN(x_out.value()); CHECK_IN(mom.value());
-      CHECK_IN(act_scale.value()); CHECK_IN(u_out.value());
-      xp_p = x_prev->data_ptr<float>();
-      xo_p = x_out->data_ptr<float>();
-      mom_p = mom->data_ptr<float>();
-      a_p = act_scale->data_ptr<float>();
-      u_p = u_out->data_ptr<float>();
-    }
-  }
-  dim3 grid(cdiv(n, bn == 256 ? 256 : BN), cdiv(B, BM), M);
+  if (mode == ENC_LISTA_FWD || mode == ENC_LISTA_BWD) TORCH_CHECK(y_in, "modes 4/5 need y_in");
+  if (mode == ENC_LISTA_FWD)
+    TORCH_CHECK(x_prev && x_out && mom && act_scale && u_out,
+                "mode 4 needs x_prev/x_out/mom/act_scale(theta)/u_out");
+  const int* ds_p = dict_sizes ? int32_ptr(*dict_sizes, "dict_sizes") : nullptr;
+  dim3 grid(cdiv(n, tile_bn(bn)), cdiv(B, BM), M);
   const TileShape shape = tile_shape(B, n, d, x.data_ptr<float>(), d, Wenc.data_ptr<float>(), d, n);
   LAUNCH_TILE_BN(k_enc_fwd_t, 8, shape, bn, bk, grid,
                  x.data_ptr<float>(), Wenc.data_ptr<float>(),
-                 bias.data_ptr<float>(), inv, c_out.data_ptr<float>(),
+                 bias.data_ptr<float>(), OPT_PTR(inv_norms), c_out.data_ptr<float>(),
                  loss_parts.data_ptr<float>(), fired.data_ptr<float>(),
-                 B, d, n, (int)mode, prio ? 1 : 0, a_p, gn_p, u_p, ds_p, x_mstride,
-                 yin_p, xp_p, xo_p, mom_p);
+                 B, d, n, (int)mode, prio ? 1 : 0, OPT_PTR(act_scale), OPT_PTR(act_gain),
+                 OPT_PTR(u_out), ds_p, x_mstride,
+                 OPT_PTR(y_in), OPT_PTR(x_prev), OPT_PTR(x_out), OPT_PTR(mom));
 }
 
 void dec_fwd(torch::Tensor c, torch::Tensor Wdec, torch::Tensor inv_norms,
@@ -172,13 +163,9 @@ void dec_fwd(torch::Tensor c, torch::Tensor Wdec, torch::Tensor inv_norms,
   CHECK_IN(c); CHECK_IN(Wdec); CHECK_IN(inv_norms); CHECK_IN(x);
   CHECK_IN(r_out); CHECK_IN(loss_parts);
   int M = Wdec.size(0), n = Wdec.size(1), d = Wdec.size(2);
-  long x_mstride = 0;
-  if (x.dim() == 3) {
-    TORCH_CHECK(x.size(0) == M, "per-model x must be [M,B,d]");
-    x_mstride = (long)x.size(1) * x.size(2);
-  }
+  const long x_mstride = x_model_stride(x, M);
   int B = x.size(x.dim() - 2);
-  dim3 grid(cdiv(d, bn == 256 ? 256 : BN), cdiv(B, BM), M);
+  dim3 grid(cdiv(d, tile_bn(bn)), cdiv(B, BM), M);
   const TileShape shape = tile_shape(B, d, n, c.data_ptr<float>(), n, Wdec.data_ptr<float>(), d, d);
   // the aligned TBK=16 kernel needs scratch at 8 waves/SIMD: it keeps 6
   LAUNCH_TILE_BN(k_dec_fwd_t, 6, shape, bn, bk, grid,
@@ -196,14 +183,14 @@ void gc(torch::Tensor r, torch::Tensor Wdec, torch::Tensor inv_norms,
   CHECK_IN(l1_alpha); CHECK_IN(gpre); CHECK_IN(g_bias);
   int M = Wdec.size(0), n = Wdec.size(1), d = Wdec.size(2);
   int B = r.size(1);
-  dim3 grid(cdiv(n, bn == 256 ? 256 : BN), cdiv(B, BM), M);
-  // gc_mode 0: the kernel stores one column sum per 32-row group; they are
+  dim3 grid(cdiv(n, tile_bn(bn)), cdiv(B, BM), M);
+  // GC_RELU: the kernel stores one column sum per 32-row group; they are
   // added into g_bias in a fixed order below (reproducible bias gradient);
   // accumulate=false overwrites g_bias, so the caller need not zero it
   const int nrg = cdiv(B, 32);
   torch::Tensor part;
   float* part_p = nullptr;
-  if (gc_mode == 0) {
+  if (gc_mode == GC_RELU) {
     TORCH_CHECK(g_bias.numel() == (long)M * n, "g_bias must be [M, n]");
     part = torch::empty({M, nrg, n}, r.options());
     part_p = part.data_ptr<float>();
@@ -214,7 +201,7 @@ void gc(torch::Tensor r, torch::Tensor Wdec, torch::Tensor inv_norms,
                  inv_norms.data_ptr<float>(), c.data_ptr<float>(),
                  l1_alpha.data_ptr<float>(), gpre.data_ptr<float>(),
                  part_p, B, d, n, prio ? 1 : 0, (int)gc_mode);
-  if (gc_mode == 0) {
+  if (gc_mode == GC_RELU) {
     long total = (long)M * n;
     hipLaunchKernelGGL(k_colsum_groups, dim3(cdiv(total, WAVE)), dim3(256), 0, cur_stream(),
                        part_p, g_bias.data_ptr<float>(), nrg, n, total, accumulate ? 1 : 0);
@@ -257,7 +244,7 @@ void grad_w(torch::Tensor P, torch::Tensor Q, torch::Tensor gw,
   } else {
     q_stride = 0;  // shared across models
   }
-  dim3 grid(cdiv(d, bn == 256 ? 256 : BN), cdiv(n, BM), M);
+  dim3 grid(cdiv(d, tile_bn(bn)), cdiv(n, BM), M);
   const TileShape shape = tile_shape(n, d, B, P.data_ptr<float>(), n, Q.data_ptr<float>(), d, d);
   LAUNCH_TILE_BN(k_grad_w_t, 8, shape, bn, bk, grid,
                  P.data_ptr<float>(), p_stride, Q.data_ptr<float>(),
@@ -273,11 +260,7 @@ void project_adam(torch::Tensor W, torch::Tensor gw, torch::Tensor norms,
                   c10::optional<torch::Tensor> lr_mult) {
   CHECK_IN(W); CHECK_IN(gw); CHECK_IN(norms); CHECK_IN(mu); CHECK_IN(nu);
   CHECK_IN(step_no);
-  const float* wu = nullptr;
-  if (w_used.has_value()) {
-    CHECK_IN(w_used.value());
-    wu = w_used->data_ptr<float>();
-  }
+  const float* wu = OPT_PTR(w_used);
   long rows = W.numel() / W.size(-1);
   const float* lrm = nullptr;
   if (lr_mult.has_value()) {
@@ -362,12 +345,7 @@ void enc_fwd2(torch::Tensor xT, torch::Tensor WT, torch::Tensor bias,
   int M = WT.size(0), d = WT.size(1), n = WT.size(2);
   int B = xT.size(1);
   TORCH_CHECK(B % 4 == 0 && n % 4 == 0, "B and n must be multiples of 4");
-  const int* ds_p = nullptr;
-  if (dict_sizes.has_value()) {
-    TORCH_CHECK(dict_sizes->is_cuda() && dict_sizes->is_contiguous() &&
-                dict_sizes->scalar_type() == torch::kInt32, "dict_sizes must be int32 GPU");
-    ds_p = dict_sizes->data_ptr<int>();
-  }
+  const int* ds_p = dict_sizes ? int32_ptr(*dict_sizes, "dict_sizes") : nullptr;
   dim3 grid(cdiv(n, BN), cdiv(B, BM), M);
   LAUNCH_TILE_GUARDED(k_enc_fwd2_t, bk, grid,
               xT.data_ptr<float>(), WT.data_ptr<float>(),
@@ -394,13 +372,11 @@ void gc2(torch::Tensor rT, torch::Tensor WT, torch::Tensor c,
 void topk_select(torch::Tensor scores, torch::Tensor c_out, torch::Tensor fired,
                  torch::Tensor ks) {
   CHECK_IN(scores); CHECK_IN(c_out); CHECK_IN(fired);
-  TORCH_CHECK(ks.is_cuda() && ks.is_contiguous() && ks.scalar_type() == torch::kInt32,
-              "ks must be int32 GPU");
   int M = scores.size(0), B = scores.size(1), n = scores.size(2);
   dim3 grid(B, 1, M);
   hipLaunchKernelGGL(k_topk_select, grid, dim3(TOPK_T), 0, cur_stream(),
                      scores.data_ptr<float>(), c_out.data_ptr<float>(),
-                     fired.data_ptr<float>(), ks.data_ptr<int>(), B, n);
+                     fired.data_ptr<float>(), int32_ptr(ks, "ks"), B, n);
 }
 
 void resample(torch::Tensor fired, torch::Tensor new_rows, torch::Tensor enc_scale,
@@ -412,8 +388,6 @@ void resample(torch::Tensor fired, torch::Tensor new_rows, torch::Tensor enc_sca
               torch::Tensor counts_out) {
   CHECK_IN(fired); CHECK_IN(new_rows); CHECK_IN(enc_scale);
   CHECK_IN(W); CHECK_IN(mu_w); CHECK_IN(nu_w);
-  TORCH_CHECK(counts_out.is_cuda() && counts_out.scalar_type() == torch::kInt32,
-              "counts_out must be int32 GPU");
   int M = W.size(0), n = W.size(1), d = W.size(2);
   int n_track = new_rows.size(1);
   float* dec_p = nullptr; float* mud_p = nullptr; float* nud_p = nullptr;
@@ -435,7 +409,7 @@ void resample(torch::Tensor fired, torch::Tensor new_rows, torch::Tensor enc_sca
                      enc_scale.data_ptr<float>(), W.data_ptr<float>(),
                      mu_w.data_ptr<float>(), nu_w.data_ptr<float>(),
                      dec_p, mud_p, nud_p, b_p, mub_p, nub_p,
-                     counts_out.data_ptr<int>(), n, d, n_track);
+                     int32_ptr(counts_out, "counts_out"), n, d, n_track);
 }
 
 void lista_bwd_elem(torch::Tensor g_y, c10::optional<torch::Tensor> carry_in,
@@ -445,11 +419,7 @@ void lista_bwd_elem(torch::Tensor g_y, c10::optional<torch::Tensor> carry_in,
                     torch::Tensor g_theta, torch::Tensor g_rho) {
   CHECK_IN(g_y); CHECK_IN(r); CHECK_IN(theta); CHECK_IN(x); CHECK_IN(x_prev);
   CHECK_IN(mom); CHECK_IN(g_r); CHECK_IN(carry_out); CHECK_IN(g_theta); CHECK_IN(g_rho);
-  const float* ci = nullptr;
-  if (carry_in.has_value()) {
-    CHECK_IN(carry_in.value());
-    ci = carry_in->data_ptr<float>();
-  }
+  const float* ci = OPT_PTR(carry_in);
   int M = g_y.size(0), B = g_y.size(1), n = g_y.size(2);
   dim3 grid(cdiv(n, LBW_COLS), cdiv(B, LBW_ROWS), M);
   hipLaunchKernelGGL(k_lista_bwd_elem, grid, dim3(LBW_COLS), 0, cur_stream(),
