@@ -63,6 +63,12 @@ def build(sig_name, d, n, M, device):
         sig = TopKEncoder
         models = [TopKEncoder.init(d, n, 32) for _ in range(M)]
         no_stacking = True  # vmap can't stack data-dependent topk
+    elif sig_name == "batch_topk":
+        from sparse_coding_amd.models.batch_topk import BatchTopKEncoder
+
+        sig = BatchTopKEncoder
+        models = [BatchTopKEncoder.init(d, n, 32) for _ in range(M)]
+        no_stacking = True  # the selection is data-dependent, as for topk
     elif sig_name == "lista":
         sig = FunctionalLISTADenoisingSAE
         models = [sig.init(d, n, 3, float(l1)) for l1 in l1s]
@@ -111,16 +117,16 @@ def main():
     p.add_argument("--d-model", type=int, default=512)
     p.add_argument("--dict-size", type=int, default=4096)
     p.add_argument("--n-models", type=int, default=8)
-    p.add_argument("--only", default="", help="run just one signature")
+    p.add_argument("--only", default="", help="run just these signatures (comma-separated)")
     p.add_argument("--backend", default="", help="run just one backend (hip|torch)")
     args = p.parse_args()
     device = "cuda:0"
 
     sig_names = ("tied", "untied", "masked_tied", "thresholding", "reverse",
-                 "centered", "whitened", "positive", "topk", "lista",
+                 "centered", "whitened", "positive", "topk", "batch_topk", "lista",
                  "residual", "semilinear")
     if args.only:
-        sig_names = tuple(s for s in sig_names if s == args.only)
+        sig_names = tuple(s for s in sig_names if s in args.only.split(","))
     backends = (args.backend,) if args.backend else ("hip", "torch")
     for sig_name in sig_names:
         row = {"sig": sig_name}

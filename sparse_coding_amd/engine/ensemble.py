@@ -213,6 +213,11 @@ class FunctionalEnsemble:
             leaf.copy_(new_leaf)
 
         fx_optim.apply_updates(self.params, updates)
+        # signatures with non-gradient training state (BatchTopK's inference
+        # threshold) update their stacked buffers in place after the step
+        update_buffers = getattr(self.sig, "update_buffers", None)
+        if update_buffers is not None:
+            update_buffers(self.buffers, aux_data)
         return loss_data, aux_data
 
     # convenience: gradient-only pass, used by the DP trainer to insert an

@@ -20,10 +20,13 @@ hand-written gfx950 HIP kernels (``sparse_coding_amd/ops/hip/sae_kernels.hip``):
                    decoder renormalization) + fused Adam; optional separate
                    "used" weights + clamp-derivative mask (positive SAE)
   k_bias_adam    : Adam on any [M,k] vector param (+ L2-decay gradient)
+  k_topk_select  : per-row radix top-k + scatter (TopK)
+  k_btk_hist/k_btk_write : batch-level radix top-k over many workgroups +
+                   scatter + inference-threshold state (BatchTopK)
 
 Fused-step coverage: EVERY trainable signature in the zoo — tied, untied,
 masked tied/untied, thresholding, reverse, tied-centered, positive-tied,
-TopK, LISTA, residual-denoising and semilinear.
+TopK, BatchTopK, LISTA, residual-denoising and semilinear.
 
 Structure.  Every step class derives from ``_HipStep``, which owns what
 does not depend on the signature: the Adam hyper-parameters, the kernel
@@ -97,6 +100,7 @@ def maybe_make_step(ensemble, required: bool = False) -> Optional["_HipStep"]:
             raise RuntimeError(f"backend='hip' requested but ensemble device is {dev}")
         return None
 
+    from sparse_coding_amd.models.batch_topk import BatchTopKEncoder
     from sparse_coding_amd.models.lista import (
         FunctionalLISTADenoisingSAE,
         FunctionalResidualDenoisingSAE,
@@ -110,6 +114,7 @@ def maybe_make_step(ensemble, required: bool = False) -> Optional["_HipStep"]:
 
     make = {
         TopKEncoder: HipTopKStep,
+        BatchTopKEncoder: HipBatchTopKStep,
         sigs.FunctionalThresholdingSAE: HipThresholdStep,
         sigs.FunctionalReverseSAE: sae(tied=True, reverse=True),
         sigs.FunctionalTiedCenteredSAE: HipCenteredStep,
@@ -1051,9 +1056,7 @@ class HipTopKStep(_HipStep):
         ext.row_norms(W, self.norms, self.inv_norms, self.EPS)
         ext.enc_fwd(x, W, self.dummy_bias, self.inv_norms,
                     self.scores, self.loss_parts, self.fired, 1, bk, prio)
-        # exact per-row radix top-k + scatter + fired counts in ONE kernel
-        # (k_topk_select) — replaces the torch.topk/scatter chain
-        ext.topk_select(self.scores, self.c, self.fired, self.ks_i32)
+        self._select()
 
         ext.dec_fwd(self.c, W, self.inv_norms, x, self.r, self.loss_parts, self.bk_dec, prio)
         ext.gc(self.r, W, self.inv_norms, self.c, self.zero_l1,
@@ -1062,6 +1065,12 @@ class HipTopKStep(_HipStep):
         ext.grad_w(self.c, self.r, self.gw, gscale, 0.0, bk_gw, prio)
         ext.grad_w(self.gpre, x, self.gw, 1.0, 1.0, bk_gw, prio)
         _announce(on_grads, self.gw)
+
+    def _select(self):
+        """scores -> codes c (+ fired counts)."""
+        # exact per-row radix top-k + scatter + fired counts in ONE kernel
+        # (k_topk_select) — replaces the torch.topk/scatter chain
+        self.ext.topk_select(self.scores, self.c, self.fired, self.ks_i32)
 
     def update_phase(self, B: int):
         t = self._begin_update()
@@ -1073,3 +1082,63 @@ class HipTopKStep(_HipStep):
 
     def dp_grad_tensors(self):
         return [self.gw]
+
+
+class HipBatchTopKStep(HipTopKStep):
+    """Fused BatchTopK training step: the TopK chain with the per-row
+    selection replaced by a batch-level one (models/batch_topk.py).
+
+    Per model the K = min(k*B, B*n) largest of all B*n scores are kept, ties
+    at the K-th value included.  The selection is an exact multi-workgroup
+    radix select (k_btk_hist x3 + k_btk_write behind ext.batch_topk_select):
+    no host read, K computed on the device, captured in the step's hipGraph
+    with the rest of the chain.  The write pass also reports the batch's
+    selection threshold (``thr_batch``, returned as loss_data["threshold"])
+    and folds it into the inference-threshold state.
+
+    That state (buffers "threshold", "threshold_n", "threshold_lr") is read
+    from ``ens.buffers`` at every launch, not at construction: a resumed
+    sweep replaces the whole buffer tree.  A captured graph holds the
+    buffers' addresses, so when they change the graph is dropped and
+    captured again.
+
+    Under data parallelism each rank selects on its local batch and keeps
+    its own threshold state; the thresholds are not synchronised across
+    ranks.
+    """
+
+    _STATE = ("threshold", "threshold_n", "threshold_lr")
+
+    def __init__(self, ensemble, ext):
+        super().__init__(ensemble, ext)
+        self._captured_state = None
+
+    def _alloc_workspaces(self, B: int):
+        super()._alloc_workspaces(B)
+        M = self.n_models
+        self.thr_batch = self._empty(M)
+        self.btk_work = torch.empty(self.ext.batch_topk_workspace_size(M), device=self._dev,
+                                    dtype=torch.int32)
+
+    def _state_ptrs(self):
+        return tuple(self.ens.buffers[k].data_ptr() for k in self._STATE)
+
+    def _select(self):
+        b = self.ens.buffers
+        self.ext.batch_topk_select(self.scores, self.c, self.fired, self.ks_i32,
+                                   self.thr_batch, self.btk_work,
+                                   threshold=b["threshold"], threshold_n=b["threshold_n"],
+                                   threshold_lr=b["threshold_lr"])
+
+    def _capture(self, x):
+        super()._capture(x)
+        self._captured_state = self._state_ptrs()
+
+    def step(self, minibatches, expand_dims: bool = True):
+        if self._graph is not None and self._captured_state != self._state_ptrs():
+            self._graph = None  # the buffer tree was replaced: capture again
+        return super().step(minibatches, expand_dims=expand_dims)
+
+    def _loss_data(self, B: int):
+        mse = self.loss_parts[:, 0] / (B * self.d_act)
+        return {"loss": mse, "threshold": self.thr_batch}

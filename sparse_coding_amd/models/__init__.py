@@ -8,3 +8,4 @@ from sparse_coding_amd.models.sae_signatures import (
     FunctionalMaskedSAE, FunctionalReverseSAE,
 )
 from sparse_coding_amd.models.topk import TopKEncoder, TopKLearnedDict
+from sparse_coding_amd.models.batch_topk import BatchTopKEncoder, BatchTopKLearnedDict

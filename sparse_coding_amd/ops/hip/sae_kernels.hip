@@ -66,7 +66,8 @@
 //   k_grad_w_t   : gw = beta*gw + alpha * P^T @ Q   (K = batch contraction)
 //   k_row_norms, k_project_adam (gradient of w/max(||w||,eps)), k_bias_adam,
 //   k_transpose_scale, k_colsum (HBM-rate column sums / L1 reductions),
-//   k_topk_select (exact per-row radix top-k), k_resample (K14 on-device),
+//   k_topk_select (exact per-row radix top-k), k_btk_hist/k_btk_write (exact
+//   batch-level radix top-k over many workgroups), k_resample (K14 on-device),
 //   k_lista_bwd_elem (one-pass LISTA backward elementwise chain)
 
 #include <hip/hip_runtime.h>
@@ -1063,6 +1064,261 @@ void k_topk_select(const float* __restrict__ scores,  // [M, B, n]
     }
     c[j] = v;
   }
+}
+
+// ---------------------------------------------------------------------------
+// k_btk_hist / k_btk_write: batch-level top-k selection for the BatchTopK
+// encoder.  Per model, the K = min(k*B, B*n) largest of ALL B*n scores are
+// kept (not k per row): t = the K-th largest score of the whole matrix,
+//   c[b,j] = (s[b,j] >= t && s[b,j] > 0) ? s[b,j] : +0
+// with every exact tie at t kept, so the result does not depend on any order.
+//
+// B*n is millions of scores per model, so the exact radix select over the
+// f32_ord keys runs across many workgroups per model (blockIdx.z = model),
+// split over kernel launches on one stream; no workgroup ever waits for
+// another.  Three histogram passes, MSB first, 11 + 11 + 10 bits:
+//   k_btk_hist<P>: every block counts its grid-stride slice of the scores
+//     whose key matches the prefix decided so far into an LDS histogram
+//     (BTK_R lane-interleaved copies per bin: scores cluster in a few
+//     exponent buckets, and lanes of one wave that hit the same bin would
+//     serialise on one LDS address), then adds its non-empty bins to the
+//     model's global histogram of that pass: integer atomics, one per bin
+//     and block.
+//   The bin holding the K-th element of pass P is picked at the head of the
+//     next launch, by every block redundantly (btk_pick, a block-wide scan
+//     from the top bin down); block 0 records (prefix, rank left) in the
+//     workspace for the launch after that, so each launch picks once.
+//   k_btk_write: picks the last bin -> the exact key of t; one pass writes c
+//     and the fired counts; block 0 reports t and folds max(t, 0) into the
+//     running inference threshold.
+// Scores are read as float4 where the model's base pointer allows it, with a
+// scalar tail (and a scalar loop otherwise): the counts are the same.
+//
+// Workspace, int32, BTK_WORK per model, zeroed by the launcher before the
+// first pass: hist0[2048] hist1[2048] hist2[1024] state[BTK_STATE].
+// ---------------------------------------------------------------------------
+#define BTK_T 256
+#define BTK_R 4
+#define BTK_BINS0 2048
+#define BTK_BINS1 2048
+#define BTK_BINS2 1024
+#define BTK_HIST1 BTK_BINS0
+#define BTK_HIST2 (BTK_BINS0 + BTK_BINS1)
+#define BTK_STATE_OFF (BTK_BINS0 + BTK_BINS1 + BTK_BINS2)
+#define BTK_STATE 8  // (prefix, rank left) after pass 0 and after pass 1
+#define BTK_WORK (BTK_STATE_OFF + BTK_STATE)
+
+__device__ __forceinline__ float f32_unord(unsigned u) {
+  return __uint_as_float((u & 0x80000000u) ? (u ^ 0x80000000u) : ~u);
+}
+
+// K of one model: min(k * B, B * n), 0 for k <= 0
+__device__ __forceinline__ long btk_K(int k, int B, long Nm) {
+  if (k <= 0) return 0;
+  long K = (long)k * B;
+  return K < Nm ? K : Nm;
+}
+
+// The bin of the global histogram gh[nbins] that holds the kleft-th largest
+// counted element, scanning from the top bin down: out[0] = bin, out[1] =
+// its rank inside that bin.  Whole block, nbins = BTK_T * PER.
+template <int PER>
+__device__ __forceinline__ void btk_pick(const unsigned* __restrict__ gh, unsigned kleft,
+                                         unsigned* sh_scan, unsigned* out) {
+  const int t = threadIdx.x;
+  const int top = BTK_T * PER - 1 - t * PER;  // this thread's highest bin
+  unsigned cnt[PER];
+  unsigned part = 0u;
+#pragma unroll
+  for (int i = 0; i < PER; ++i) {
+    cnt[i] = gh[top - i];
+    part += cnt[i];
+  }
+  if (t == 0) {  // defensive: the counts always reach kleft
+    out[0] = 0u;
+    out[1] = kleft;
+  }
+  unsigned v = part;  // inclusive count from the top bin through this thread's
+  for (int off = 1; off < BTK_T; off <<= 1) {
+    sh_scan[t] = v;
+    __syncthreads();
+    if (t >= off) v += sh_scan[t - off];
+    __syncthreads();
+  }
+  const unsigned excl = v - part;
+  if (excl < kleft && kleft <= v) {  // one thread
+    unsigned left = kleft - excl;
+    int i = 0;
+    for (; i < PER - 1; ++i) {
+      if (cnt[i] >= left) break;
+      left -= cnt[i];
+    }
+    out[0] = (unsigned)(top - i);
+    out[1] = left;
+  }
+  __syncthreads();
+}
+
+template <int SHIFT, int NBINS>
+__device__ __forceinline__ void btk_count(unsigned* hist, float s, unsigned mask,
+                                          unsigned prefix, int rep) {
+  unsigned u = f32_ord(s);
+  if ((u & mask) == prefix) atomicAdd(&hist[((u >> SHIFT) & (NBINS - 1)) * BTK_R + rep], 1u);
+}
+
+template <int PASS>
+__global__ __launch_bounds__(BTK_T)
+void k_btk_hist(const float* __restrict__ scores,  // [M, B, n]
+                const int* __restrict__ ks,        // [M]
+                unsigned* __restrict__ work,       // [M, BTK_WORK]
+                int B, int n) {
+  constexpr int SHIFT = PASS == 0 ? 21 : (PASS == 1 ? 10 : 0);
+  constexpr int NBINS = PASS == 0 ? BTK_BINS0 : (PASS == 1 ? BTK_BINS1 : BTK_BINS2);
+  constexpr int HOFF = PASS == 0 ? 0 : (PASS == 1 ? BTK_HIST1 : BTK_HIST2);
+  constexpr unsigned MASK = PASS == 0 ? 0u : (PASS == 1 ? 0xFFE00000u : 0xFFFFFC00u);
+
+  const int m = blockIdx.z;
+  const int t = threadIdx.x;
+  const long Nm = (long)B * n;
+  const long K = btk_K(ks[m], B, Nm);
+  if (K == 0) return;  // whole block: nothing is selected
+  unsigned* work_m = work + (long)m * BTK_WORK;
+
+  __shared__ __attribute__((aligned(16))) unsigned hist[NBINS * BTK_R];
+  __shared__ unsigned sh_scan[BTK_T];
+  __shared__ unsigned sh_pick[2];
+
+  for (int i = t; i < NBINS * BTK_R; i += BTK_T) hist[i] = 0u;
+
+  unsigned prefix = 0u;
+  if (PASS == 1) {
+    btk_pick<BTK_BINS0 / BTK_T>(work_m, (unsigned)K, sh_scan, sh_pick);
+    prefix = sh_pick[0] << 21;
+    if (blockIdx.x == 0 && t == 0) {
+      work_m[BTK_STATE_OFF + 0] = prefix;
+      work_m[BTK_STATE_OFF + 1] = sh_pick[1];
+    }
+  } else if (PASS == 2) {
+    prefix = work_m[BTK_STATE_OFF + 0];
+    btk_pick<BTK_BINS1 / BTK_T>(work_m + BTK_HIST1, work_m[BTK_STATE_OFF + 1], sh_scan, sh_pick);
+    prefix |= sh_pick[0] << 10;
+    if (blockIdx.x == 0 && t == 0) {
+      work_m[BTK_STATE_OFF + 2] = prefix;
+      work_m[BTK_STATE_OFF + 3] = sh_pick[1];
+    }
+  }
+  __syncthreads();  // hist zeroed (the picks end on a barrier as well)
+
+  const float* s = scores + (long)m * Nm;
+  const int rep = t & (BTK_R - 1);
+  const long stride = (long)gridDim.x * BTK_T;
+  const long first = (long)blockIdx.x * BTK_T + t;
+  const bool vec = (reinterpret_cast<uintptr_t>(s) & 15) == 0;
+  const long nvec = vec ? (Nm >> 2) : 0;
+  const float4* s4 = reinterpret_cast<const float4*>(s);
+  long i = first;
+  for (; i + 3 * stride < nvec; i += 4 * stride) {  // four loads in flight
+    float4 v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) v[q] = s4[i + q * stride];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      btk_count<SHIFT, NBINS>(hist, v[q].x, MASK, prefix, rep);
+      btk_count<SHIFT, NBINS>(hist, v[q].y, MASK, prefix, rep);
+      btk_count<SHIFT, NBINS>(hist, v[q].z, MASK, prefix, rep);
+      btk_count<SHIFT, NBINS>(hist, v[q].w, MASK, prefix, rep);
+    }
+  }
+  for (; i < nvec; i += stride) {
+    float4 v = s4[i];
+    btk_count<SHIFT, NBINS>(hist, v.x, MASK, prefix, rep);
+    btk_count<SHIFT, NBINS>(hist, v.y, MASK, prefix, rep);
+    btk_count<SHIFT, NBINS>(hist, v.z, MASK, prefix, rep);
+    btk_count<SHIFT, NBINS>(hist, v.w, MASK, prefix, rep);
+  }
+  for (long j = (nvec << 2) + first; j < Nm; j += stride)
+    btk_count<SHIFT, NBINS>(hist, s[j], MASK, prefix, rep);
+  __syncthreads();
+
+  unsigned* gh = work_m + HOFF;
+  const uint4* hist4 = reinterpret_cast<const uint4*>(hist);  // BTK_R == 4 copies
+  for (int bin = t; bin < NBINS; bin += BTK_T) {
+    uint4 h = hist4[bin];
+    unsigned c = h.x + h.y + h.z + h.w;
+    if (c) atomicAdd(&gh[bin], c);
+  }
+}
+
+__device__ __forceinline__ float btk_keep(float s, unsigned thr, float* __restrict__ fired_m,
+                                          long idx, int n) {
+  if (f32_ord(s) >= thr && s > 0.f) {
+    atomicAdd(&fired_m[idx % n], 1.f);  // whole numbers: exact in any order
+    return s;
+  }
+  return 0.f;
+}
+
+__global__ __launch_bounds__(BTK_T)
+void k_btk_write(const float* __restrict__ scores,  // [M, B, n]
+                 float* __restrict__ c_out,         // [M, B, n]
+                 float* __restrict__ fired,         // [M, n]
+                 const int* __restrict__ ks,        // [M]
+                 float* __restrict__ thr_out,       // [M]
+                 const unsigned* __restrict__ work, // [M, BTK_WORK]
+                 float* __restrict__ theta,         // [M] or null
+                 int* __restrict__ theta_n,         // [M] or null
+                 const float* __restrict__ theta_lr,  // [M] or null
+                 int B, int n) {
+  const int m = blockIdx.z;
+  const int t = threadIdx.x;
+  const long Nm = (long)B * n;
+  const long K = btk_K(ks[m], B, Nm);
+  const unsigned* work_m = work + (long)m * BTK_WORK;
+
+  __shared__ unsigned sh_scan[BTK_T];
+  __shared__ unsigned sh_pick[2];
+
+  // K == 0 keeps nothing: no key reaches 0xFFFFFFFF with s > 0 (that is a NaN)
+  unsigned thr = 0xFFFFFFFFu;
+  if (K != 0) {
+    btk_pick<BTK_BINS2 / BTK_T>(work_m + BTK_HIST2, work_m[BTK_STATE_OFF + 3], sh_scan, sh_pick);
+    thr = work_m[BTK_STATE_OFF + 2] | sh_pick[0];
+  }
+
+  if (blockIdx.x == 0 && t == 0) {
+    const float tval = K != 0 ? f32_unord(thr) : __uint_as_float(0x7F800000u);
+    thr_out[m] = tval;
+    if (theta != nullptr && K != 0) {
+      const float stat = fmaxf(tval, 0.f);
+      const int cnt = theta_n[m];
+      float th = theta[m];
+      if (cnt == 0) th = stat;
+      else if (stat != th) th = fmaf(theta_lr[m], stat - th, th);  // two roundings
+      theta[m] = th;
+      theta_n[m] = cnt + 1;
+    }
+  }
+
+  const float* s = scores + (long)m * Nm;
+  float* c = c_out + (long)m * Nm;
+  float* fired_m = fired + (long)m * n;
+  const long stride = (long)gridDim.x * BTK_T;
+  const long first = (long)blockIdx.x * BTK_T + t;
+  const bool vec = ((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(c)) & 15) == 0;
+  const long nvec = vec ? (Nm >> 2) : 0;
+  const float4* s4 = reinterpret_cast<const float4*>(s);
+  float4* c4 = reinterpret_cast<float4*>(c);
+  for (long i = first; i < nvec; i += stride) {
+    float4 v = s4[i];
+    float4 o;
+    o.x = btk_keep(v.x, thr, fired_m, 4 * i + 0, n);
+    o.y = btk_keep(v.y, thr, fired_m, 4 * i + 1, n);
+    o.z = btk_keep(v.z, thr, fired_m, 4 * i + 2, n);
+    o.w = btk_keep(v.w, thr, fired_m, 4 * i + 3, n);
+    c4[i] = o;
+  }
+  for (long j = (nvec << 2) + first; j < Nm; j += stride)
+    c[j] = btk_keep(s[j], thr, fired_m, j, n);
 }
 
 // ---------------------------------------------------------------------------

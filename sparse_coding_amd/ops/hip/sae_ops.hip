@@ -379,6 +379,58 @@ void topk_select(torch::Tensor scores, torch::Tensor c_out, torch::Tensor fired,
                      fired.data_ptr<float>(), int32_ptr(ks, "ks"), B, n);
 }
 
+// int32 elements of workspace batch_topk_select needs for M models
+int64_t batch_topk_workspace_size(int64_t M) { return M * (int64_t)BTK_WORK; }
+
+// Batch-level top-k: a zeroing of the workspace, three histogram passes and
+// one write pass, all on the current stream (capturable; no host read).  K =
+// min(ks[m] * B, B * n) is computed on the device.
+void batch_topk_select(torch::Tensor scores, torch::Tensor c_out, torch::Tensor fired,
+                       torch::Tensor ks, torch::Tensor thr_out, torch::Tensor work,
+                       c10::optional<torch::Tensor> threshold,
+                       c10::optional<torch::Tensor> threshold_n,
+                       c10::optional<torch::Tensor> threshold_lr) {
+  CHECK_IN(scores); CHECK_IN(c_out); CHECK_IN(fired); CHECK_IN(thr_out);
+  TORCH_CHECK(scores.dim() == 3, "scores must be [M,B,n]");
+  TORCH_CHECK(c_out.sizes() == scores.sizes(), "c_out must have the shape of scores");
+  const long M = scores.size(0), B = scores.size(1), n = scores.size(2);
+  TORCH_CHECK(B * n < (1L << 31), "batch_topk_select: B*n per model must be below 2^31");
+  TORCH_CHECK(M <= 65535, "batch_topk_select: at most 65535 models");
+  TORCH_CHECK(fired.numel() == M * n, "fired must be [M,n]");
+  TORCH_CHECK(ks.numel() == M && thr_out.numel() == M, "ks and thr_out must be [M]");
+  TORCH_CHECK(work.numel() >= batch_topk_workspace_size(M),
+              "work needs batch_topk_workspace_size(M) int32 elements");
+  const int* ks_p = int32_ptr(ks, "ks");
+  unsigned* work_p = reinterpret_cast<unsigned*>(int32_ptr(work, "work"));
+  const bool has_thr = threshold.has_value();
+  TORCH_CHECK(threshold_n.has_value() == has_thr && threshold_lr.has_value() == has_thr,
+              "threshold, threshold_n and threshold_lr go together");
+  float* th_p = nullptr; int* thn_p = nullptr; const float* thlr_p = nullptr;
+  if (has_thr) {
+    CHECK_IN(threshold.value()); CHECK_IN(threshold_lr.value());
+    TORCH_CHECK(threshold->numel() == M && threshold_n->numel() == M && threshold_lr->numel() == M,
+                "threshold state must be [M]");
+    th_p = threshold->data_ptr<float>();
+    thn_p = int32_ptr(*threshold_n, "threshold_n");
+    thlr_p = threshold_lr->data_ptr<float>();
+  }
+  if (M == 0 || B * n == 0) return;
+
+  // a block takes at least 16 elements per thread; about four blocks per CU in all
+  const long cap = std::max(1L, 1024 / M);
+  dim3 grid((unsigned)std::min(cap, (B * n + BTK_T * 16 - 1) / (BTK_T * 16)), 1, (unsigned)M);
+  hipStream_t st = cur_stream();
+  TORCH_CHECK(hipMemsetAsync(work_p, 0, sizeof(int) * batch_topk_workspace_size(M), st) == hipSuccess,
+              "batch_topk_select: zeroing the workspace failed");
+  const float* s_p = scores.data_ptr<float>();
+  hipLaunchKernelGGL(k_btk_hist<0>, grid, dim3(BTK_T), 0, st, s_p, ks_p, work_p, (int)B, (int)n);
+  hipLaunchKernelGGL(k_btk_hist<1>, grid, dim3(BTK_T), 0, st, s_p, ks_p, work_p, (int)B, (int)n);
+  hipLaunchKernelGGL(k_btk_hist<2>, grid, dim3(BTK_T), 0, st, s_p, ks_p, work_p, (int)B, (int)n);
+  hipLaunchKernelGGL(k_btk_write, grid, dim3(BTK_T), 0, st, s_p, c_out.data_ptr<float>(),
+                     fired.data_ptr<float>(), ks_p, thr_out.data_ptr<float>(), work_p,
+                     th_p, thn_p, thlr_p, (int)B, (int)n);
+}
+
 void resample(torch::Tensor fired, torch::Tensor new_rows, torch::Tensor enc_scale,
               torch::Tensor W, torch::Tensor mu_w, torch::Tensor nu_w,
               c10::optional<torch::Tensor> dec,
@@ -456,6 +508,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x_out") = py::none(), py::arg("mom") = py::none());
   m.def("topk_select", &topk_select, "per-row radix top-k + scatter (+fired)",
         py::arg("scores"), py::arg("c_out"), py::arg("fired"), py::arg("ks"));
+  m.def("batch_topk_workspace_size", &batch_topk_workspace_size,
+        "int32 workspace elements batch_topk_select needs", py::arg("M"));
+  m.def("batch_topk_select", &batch_topk_select,
+        "batch-level radix top-k (K = k*B per model) + scatter (+fired, threshold state)",
+        py::arg("scores"), py::arg("c_out"), py::arg("fired"), py::arg("ks"),
+        py::arg("thr_out"), py::arg("work"),
+        py::arg("threshold") = py::none(), py::arg("threshold_n") = py::none(),
+        py::arg("threshold_lr") = py::none());
   m.def("resample", &resample, "fused dead-neuron resample (K14): rank dead, rewrite rows, zero Adam state",
         py::arg("fired"), py::arg("new_rows"), py::arg("enc_scale"),
         py::arg("W"), py::arg("mu_w"), py::arg("nu_w"),

@@ -22,6 +22,7 @@ import torch
 
 from sparse_coding_amd.engine.ensemble import FunctionalEnsemble
 from sparse_coding_amd.functional.optim import adam
+from sparse_coding_amd.models.batch_topk import BatchTopKEncoder
 from sparse_coding_amd.models.sae_signatures import (
     FunctionalMaskedTiedSAE,
     FunctionalSAE,
@@ -145,6 +146,24 @@ def topk_init(cfg, ks: Sequence[int] = (4, 8, 16, 32, 64, 128)):
     )
 
 
+def batch_topk_init(cfg, ks: Sequence[int] = (4, 8, 16, 32, 64, 128)):
+    """BatchTopK encoders across (average) sparsity levels: topk_init with
+    the batch-level selection and a learned inference threshold."""
+    d = cfg.activation_width
+    devices = default_devices()
+    n_dict = int(d * cfg.learned_dict_ratio)
+    models = [BatchTopKEncoder.init(d, n_dict, int(k)) for k in ks]
+    ens = FunctionalEnsemble(models, BatchTopKEncoder, adam, {"lr": cfg.lr}, device=devices[0],
+                             no_stacking=True)
+    args = {"batch_size": cfg.batch_size, "device": devices[0], "dict_size": n_dict}
+    return (
+        [(ens, args, "batch_topk")],
+        ["dict_size"],
+        ["sparsity"],
+        {"sparsity": list(ks), "dict_size": [n_dict]},
+    )
+
+
 def thresholding_init(cfg):
     """Soft-thresholding SAEs (reference :403-494)."""
     return make_grid_ensembles(cfg, FunctionalThresholdingSAE, np.logspace(-4, -2, 8))
@@ -164,6 +183,10 @@ def run_dense_l1_range(cfg):
 
 def run_topk(cfg):
     return sweep(topk_init, cfg)
+
+
+def run_batch_topk(cfg):
+    return sweep(batch_topk_init, cfg)
 
 
 def run_across_layers(cfg, layers: Sequence[int], init: Callable = dense_l1_range_init):
