@@ -203,6 +203,10 @@ class FunctionalEnsemble:
             minibatches = minibatches.expand(self.n_models, *minibatches.shape)
 
         grads, (loss_data, aux_data) = self.calc_grads(self.params, self.buffers, minibatches)
+        self._apply(grads, aux_data)
+        return loss_data, aux_data
+
+    def _apply(self, grads, aux_data):
         updates, new_states = self.update(grads, self.optim_states)
 
         # write the new optimizer state back into the existing tensors so
@@ -216,26 +220,21 @@ class FunctionalEnsemble:
         # signatures with non-gradient training state (BatchTopK's inference
         # threshold) update their stacked buffers in place after the step
         update_buffers = getattr(self.sig, "update_buffers", None)
-        if update_buffers is not None:
+        if update_buffers is not None and aux_data is not None:
             update_buffers(self.buffers, aux_data)
-        return loss_data, aux_data
 
-    # convenience: gradient-only pass, used by the DP trainer to insert an
-    # all-reduce between grad computation and the optimizer update
+    # gradient-only pass and its counterpart, used by the DP trainer to insert
+    # an all-reduce between grad computation and the optimizer update; aux is
+    # compute_grads' aux, for the signature's buffer update
     def compute_grads(self, minibatches, expand_dims: bool = True):
         with torch.no_grad():
             if expand_dims:
                 minibatches = minibatches.expand(self.n_models, *minibatches.shape)
             return self.calc_grads(self.params, self.buffers, minibatches)
 
-    def apply_grads(self, grads):
+    def apply_grads(self, grads, aux=None):
         with torch.no_grad():
-            updates, new_states = self.update(grads, self.optim_states)
-            new_leaves, _ = tree_flatten(new_states)
-            leaves, _ = tree_flatten(self.optim_states)
-            for leaf, new_leaf in zip(leaves, new_leaves):
-                leaf.copy_(new_leaf)
-            fx_optim.apply_updates(self.params, updates)
+            self._apply(grads, aux)
 
 
 FunctionalEnsemble.__module__ = "autoencoders.ensemble"

@@ -32,7 +32,7 @@ Structure.  Every step class derives from ``_HipStep``, which owns what
 does not depend on the signature: the Adam hyper-parameters, the kernel
 configuration resolved once per workspace allocation, the
 ``grads_phase`` / ``update_phase`` / ``step`` protocol with hipGraph
-capture, and the two Adam launch helpers.  A class supplies its workspaces
+capture (``GraphReplay``), and the two Adam launch helpers.  A class supplies its workspaces
 (``_alloc_workspaces``), its kernel sequence (``_grads``), its
 ``update_phase`` and its ``_loss_data``.
 
@@ -144,6 +144,63 @@ def _announce(on_grads, *tensors):
         on_grads(list(tensors))
 
 
+class GraphReplay:
+    """Runs a body eagerly twice, then from a captured hipGraph.
+
+    Owns the static input, the graph, the eager-step count and the enabled
+    flag.  ``key()`` (``_HipStep.graph_key``) names what a captured graph
+    depends on: first the workspace allocation, then whatever else the body's
+    launches hold addresses of.  A changed key drops the graph; a new
+    allocation also restarts the eager count.  After two eager calls at the
+    current allocation the next call with that batch size captures, then
+    replays.  A failed capture, or being disabled, leaves every call eager."""
+
+    def __init__(self, key, enabled: bool, what: str):
+        self.key, self.enabled, self.what = key, enabled, what
+        self.graph = None
+        self.x_static = None
+        self.eager_steps = 0
+        self._key = None
+        self._B = None  # batch size of the last eager call
+
+    def _check_key(self):
+        key = self.key()
+        if key != self._key:
+            self.graph = None
+            if self._key is None or key[0] is not self._key[0]:
+                self.eager_steps = 0
+            self._key = key
+
+    def _capture(self, x, body):
+        try:
+            self.x_static = x.clone()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                body(self.x_static)
+            self.graph = g
+        except Exception as e:  # noqa: BLE001 - graphs are an optimization only
+            print(f"{self.what} failed ({e}); staying eager")
+            self.enabled = False
+            self.graph = None
+
+    def run(self, x: torch.Tensor, body) -> None:
+        """body(x), eagerly or as a replay of its capture."""
+        if self.enabled:
+            self._check_key()
+            if self.graph is None and self.eager_steps >= 2 and self._B == x.shape[0]:
+                self._capture(x.contiguous(), body)  # capture does not execute
+            if self.graph is not None and self.x_static.shape == x.shape:
+                self.x_static.copy_(x)
+                self.graph.replay()
+                return
+        self.graph = None
+        body(x)
+        self._check_key()  # body allocates at a new batch size: count from here
+        self.eager_steps += 1
+        self._B = x.shape[0]
+
+
 class _HipStep:
     """The signature-independent part of a fused step: hyper-parameters,
     kernel configuration, the phase/step protocol with hipGraph capture,
@@ -155,6 +212,8 @@ class _HipStep:
     staging = None
     # the parameter whose [M, n, d] shape sizes the step
     dict_key = "decoder"
+    # a data-parallel trainer may run the update on row shards (HipSAEStep)
+    row_shardable = False
 
     def __init__(self, ensemble, ext):
         self.ens = ensemble
@@ -180,11 +239,12 @@ class _HipStep:
 
         # persistent workspaces, sized lazily on first batch
         self._B = None
+        self._allocation = None
         # hipGraph capture of the whole step (single-GPU path): replayed
         # after 2 eager warmup steps; disabled via SPARSE_CODING_AMD_NO_GRAPH=1
-        self.use_graph = self.captures_graph and os.environ.get("SPARSE_CODING_AMD_NO_GRAPH") != "1"
-        self._graph = None
-        self._eager_steps = 0
+        self._replay = GraphReplay(
+            self.graph_key, self.captures_graph and os.environ.get("SPARSE_CODING_AMD_NO_GRAPH") != "1",
+            "[hip_step] hipGraph capture")
 
     # -- workspace management -------------------------------------------------
     def _empty(self, *shape):
@@ -216,8 +276,24 @@ class _HipStep:
         self.bk_gw = kc["bk_grad_w"] or self.bk
         self._alloc_workspaces(B)
         self._B = B
-        self._graph = None
-        self._eager_steps = 0
+        self._allocation = object()
+
+    def graph_key(self) -> tuple:
+        """What a captured graph of this step depends on: the workspace
+        allocation first, then any other addresses its launches hold."""
+        return (self._allocation,)
+
+    @property
+    def use_graph(self) -> bool:
+        return self._replay.enabled
+
+    @use_graph.setter
+    def use_graph(self, on: bool):
+        self._replay.enabled = on
+
+    @property
+    def _graph(self):
+        return self._replay.graph
 
     def _alloc_workspaces(self, B: int):
         raise NotImplementedError
@@ -276,11 +352,21 @@ class _HipStep:
         return p, mu, nu
 
     def _adam_matrix(self, key, grad, step_no, project, n_per_model=None, lr_mult=None,
-                     w_used=None, clamp_mask=False, eps_norm=EPS_NORM):
+                     w_used=None, clamp_mask=False, eps_norm=EPS_NORM, rows=None):
         """Adam on a matrix parameter; project=True first pushes the gradient
-        through the in-forward row renormalization (k_project_adam)."""
+        through the in-forward row renormalization (k_project_adam).
+
+        rows=(g0, k) updates rows [g0, g0+k) of the flattened [M*n, d]
+        parameter from a [k, d] gradient shard (data-parallel rs_ag): the
+        launch sees one model of k rows with the first step counter."""
         W, mu, nu = self._param_state(key)
-        self.ext.project_adam(W, grad, self.norms, mu, nu, step_no, n_per_model or self.n_dict,
+        norms = self.norms
+        if rows is not None:
+            sl = slice(rows[0], rows[0] + rows[1])
+            W, mu, nu = (t.reshape(-1, t.shape[-1])[sl] for t in (W, mu, nu))
+            norms, lr_mult = norms.reshape(-1)[sl], lr_mult.reshape(-1)[sl]
+            step_no, n_per_model = step_no.reshape(-1)[0:1], rows[1]
+        self.ext.project_adam(W, grad, norms, mu, nu, step_no, n_per_model or self.n_dict,
                               self.lr, self.beta1, self.beta2, self.eps, eps_norm, project,
                               w_used=w_used, clamp_mask=clamp_mask, lr_mult=lr_mult)
 
@@ -291,35 +377,11 @@ class _HipStep:
                            self.lr, self.beta1, self.beta2, self.eps, lr_mult=lr_mult)
 
     # -- public ---------------------------------------------------------------
-    def _capture(self, x: torch.Tensor) -> None:
-        try:
-            self.x_static = x.clone()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                B = self.grads_phase(self.x_static)
-                self.update_phase(B)
-            self._graph = g
-        except Exception as e:  # noqa: BLE001 - graphs are an optimization only
-            print(f"[hip_step] hipGraph capture failed ({e}); staying eager")
-            self.use_graph = False
-            self._graph = None
-
     def step(self, minibatches: torch.Tensor, expand_dims: bool = True):
         if not expand_dims:
             raise NotImplementedError("per-model batches not supported by the HIP step")
-        B = minibatches.shape[0]
-        if self.use_graph:
-            if self._B == B and self._graph is None and self._eager_steps >= 2:
-                self._capture(minibatches.contiguous())
-            if self._graph is not None:
-                self.x_static.copy_(minibatches)
-                self._graph.replay()
-                return self._loss_data(B), {"c": self.codes}
-        B = self.grads_phase(minibatches)
-        self.update_phase(B)
-        self._eager_steps += 1
-        return self._loss_data(B), {"c": self.codes}
+        self._replay.run(minibatches, lambda x: self.update_phase(self.grads_phase(x)))
+        return self._loss_data(minibatches.shape[0]), {"c": self.codes}
 
 
 class HipSAEStep(_HipStep):
@@ -467,15 +529,38 @@ class HipSAEStep(_HipStep):
             ext.grad_w(self.gpre, x, self.gw_enc, 1.0, 0.0, bk_gw, prio, bn)
             _announce(on_grads, self.gw_enc)
 
+    def _matrix_updates(self):
+        """(parameter key, gradient workspace, project) per matrix update."""
+        if self.tied:
+            return [("encoder", self.gw, True)]
+        return [("decoder", self.gw, True), ("encoder", self.gw_enc, False)]
+
     def update_phase(self, B: int):
         """Adam updates (projection through the renorm for the dictionary)."""
         t = self._begin_update()
-        if self.tied:
-            self._adam_matrix("encoder", self.gw, t, project=True, lr_mult=self.lr_mult)
-        else:
-            self._adam_matrix("decoder", self.gw, t, project=True, lr_mult=self.lr_mult)
-            self._adam_matrix("encoder", self.gw_enc, t, project=False, lr_mult=self.lr_mult)
+        for key, grad, project in self._matrix_updates():
+            self._adam_matrix(key, grad, t, project=project, lr_mult=self.lr_mult)
+        self._update_bias(t)
+
+    def _update_bias(self, t):
         self._adam_vector("encoder_bias", self.g_bias, t, decay=self.bias_decay, lr_mult=self.lr_mult)
+
+    # -- row-sharded update (data-parallel rs_ag) -----------------------------
+    @property
+    def row_shardable(self) -> bool:
+        """Whether update_phase is the plain table above, so that a trainer
+        may run it on row shards (_adam_matrix rows=) plus _update_bias."""
+        return type(self) is HipSAEStep and not self.masked and not self.reverse
+
+    def locate_grad(self, t: torch.Tensor):
+        """The _matrix_updates entry whose gradient workspace holds t (a
+        tensor handed to on_grads) and t's first row in its [M*n, d] view."""
+        for entry in self._matrix_updates():
+            g = entry[1]
+            off = t.storage_offset() - g.storage_offset()
+            if t.untyped_storage().data_ptr() == g.untyped_storage().data_ptr() and 0 <= off < g.numel():
+                return entry, off // self.d_act
+        raise RuntimeError("gradient tensor not in a known workspace")
 
     def _loss_data(self, B: int):
         out = self._mse_l1_loss(B, self.loss_parts[:, 1])
@@ -1109,10 +1194,6 @@ class HipBatchTopKStep(HipTopKStep):
 
     _STATE = ("threshold", "threshold_n", "threshold_lr")
 
-    def __init__(self, ensemble, ext):
-        super().__init__(ensemble, ext)
-        self._captured_state = None
-
     def _alloc_workspaces(self, B: int):
         super()._alloc_workspaces(B)
         M = self.n_models
@@ -1130,14 +1211,8 @@ class HipBatchTopKStep(HipTopKStep):
                                    threshold=b["threshold"], threshold_n=b["threshold_n"],
                                    threshold_lr=b["threshold_lr"])
 
-    def _capture(self, x):
-        super()._capture(x)
-        self._captured_state = self._state_ptrs()
-
-    def step(self, minibatches, expand_dims: bool = True):
-        if self._graph is not None and self._captured_state != self._state_ptrs():
-            self._graph = None  # the buffer tree was replaced: capture again
-        return super().step(minibatches, expand_dims=expand_dims)
+    def graph_key(self):
+        return super().graph_key() + self._state_ptrs()
 
     def _loss_data(self, B: int):
         mse = self.loss_parts[:, 0] / (B * self.d_act)

@@ -14,12 +14,14 @@ schedule rings across links while later grad GEMMs still run.
 
 from __future__ import annotations
 
+import contextlib
 import os
 from typing import List, Optional, Tuple
 
 import torch
 import torch.distributed as dist
 
+from sparse_coding_amd.engine.hip_step import GraphReplay
 from sparse_coding_amd.utils.tree import tree_flatten
 
 
@@ -41,6 +43,45 @@ def init_distributed(backend: Optional[str] = None) -> Tuple[int, int, int]:
     return rank, local_rank, world_size
 
 
+class _CommOverlap:
+    """Collectives on a side stream that overlap the compute stream: enter
+    the side stream behind what the current stream has queued, remember the
+    asynchronous works, and join both before their results are used.
+    Off-GPU there is no stream and everything runs in line.  The stream is
+    made at the first use: a trainer that issues no collective (one process)
+    must not open a second stream next to the step's."""
+
+    def __init__(self, device):
+        self.on_gpu = torch.device(device).type == "cuda"
+        self.stream = None
+        self.pending = []  # (work, tensor it lands in)
+
+    def side(self):
+        """Context for issuing collectives: the comm stream, ordered behind
+        an event recorded now on the current stream."""
+        if not self.on_gpu:
+            return contextlib.nullcontext()
+        if self.stream is None:
+            self.stream = torch.cuda.Stream()
+        ev = torch.cuda.Event()
+        ev.record()
+        self.stream.wait_event(ev)
+        return torch.cuda.stream(self.stream)
+
+    def add(self, work, tensor) -> None:
+        self.pending.append((work, tensor))
+
+    def join(self) -> list:
+        """Wait on every work, make the current stream wait for the comm
+        stream, and hand back the tensors the works landed in."""
+        pending, self.pending = self.pending, []
+        for work, _ in pending:
+            work.wait()
+        if self.stream is not None:
+            torch.cuda.current_stream().wait_stream(self.stream)
+        return [t for _, t in pending]
+
+
 class GradBucketAllReducer:
     """Flattens a fixed tree of gradient tensors into persistent buckets and
     all-reduces them (avg) on a dedicated stream.
@@ -52,7 +93,7 @@ class GradBucketAllReducer:
     grad workspaces directly when they are bucket-contiguous.
     """
 
-    def __init__(self, grads_template, bucket_bytes: int = 64 << 20, group=None):
+    def __init__(self, grads_template, bucket_bytes: int = 64 << 20, group=None, overlap=None):
         self.group = group
         leaves, _ = tree_flatten(grads_template)
         self.shapes = [g.shape for g in leaves]
@@ -71,7 +112,7 @@ class GradBucketAllReducer:
             cur_size += nb
         if cur:
             self._seal(cur, device)
-        self.comm_stream = torch.cuda.Stream() if device.type == "cuda" else None
+        self.overlap = overlap if overlap is not None else _CommOverlap(device)
 
     def _seal(self, assignment, device):
         total = sum(n for _, _, n in assignment)
@@ -85,29 +126,19 @@ class GradBucketAllReducer:
         leaves, _ = tree_flatten(grads)
         world = dist.get_world_size(self.group)
 
-        works = []
         for bucket, assignment in zip(self.buckets, self.assignments):
             for li, off, n in assignment:
                 bucket[off : off + n].copy_(leaves[li].reshape(-1), non_blocking=True)
-            if self.comm_stream is not None:
-                # per-bucket event between the (current-stream) pack copies
-                # and the (comm-stream) all_reduce — a single wait_stream at
-                # the top would not order copies issued after it
-                ev = torch.cuda.Event()
-                ev.record()
-                self.comm_stream.wait_event(ev)
-                with torch.cuda.stream(self.comm_stream):
-                    works.append((dist.all_reduce(bucket, async_op=True), bucket, assignment))
-            else:
-                works.append((dist.all_reduce(bucket, async_op=True), bucket, assignment))
-
-        for work, bucket, assignment in works:
-            work.wait()
+            # per-bucket event between the (current-stream) pack copies and
+            # the (comm-stream) all_reduce — a single wait_stream at the top
+            # would not order copies issued after it
+            with self.overlap.side():
+                self.overlap.add(dist.all_reduce(bucket, async_op=True), bucket)
+        self.overlap.join()
+        for bucket, assignment in zip(self.buckets, self.assignments):
             bucket.div_(world)
             for li, off, n in assignment:
                 leaves[li].reshape(-1).copy_(bucket[off : off + n], non_blocking=True)
-        if self.comm_stream is not None:
-            torch.cuda.current_stream().wait_stream(self.comm_stream)
 
 
 def _reduce_scatter_rows(flat: torch.Tensor, out: torch.Tensor, group) -> "dist.Work":
@@ -147,7 +178,7 @@ class DataParallelEnsembleTrainer:
 
     dp_mode:
       "allreduce" (default) — all-reduce the [M, n, d] gradients (chunked
-        over model halves, overlapped with the remaining grad GEMMs on a
+        over model quarters, overlapped with the remaining grad GEMMs on a
         side stream) and apply the full, deterministic Adam update locally;
         replicas stay bit-identical without a broadcast.
       "rs_ag" — ZeRO-style: reduce-scatter each weight-gradient chunk into
@@ -181,11 +212,22 @@ class DataParallelEnsembleTrainer:
         # to eager on capture failure.
         if graph_capture is None:
             graph_capture = os.environ.get("SC_AMD_DP_GRAPH") == "1"
-        self.graph_capture = graph_capture
-        self._graph = None
-        self._graph_B = None
-        self._graph_ws = None
-        self._dp_steps = 0
+        # same replay rules and the same invalidation key as the step's own
+        # graph (engine/hip_step.py), over the DP body
+        self._replay = GraphReplay(lambda: self.ensemble._hip_step.graph_key(),
+                                   graph_capture and torch.cuda.is_available(), "[dp] graph capture")
+        self._overlap = _CommOverlap(ensemble.device)
+        self._rs_ag_warned = False
+        self._rs_shards = {}  # (parameter key, first row) -> [k, d] gradient shard
+        self._rs_consolidate = []  # (moment tensor, first row, rows) sharded by the last rs_ag step
+
+    @property
+    def graph_capture(self) -> bool:
+        return self._replay.enabled
+
+    @property
+    def _graph(self):
+        return self._replay.graph
 
     def broadcast_state(self) -> None:
         """One-time parameter/optimizer broadcast from rank 0 (use when
@@ -197,12 +239,6 @@ class DataParallelEnsembleTrainer:
                 if leaf.dtype.is_floating_point or leaf.dtype in (torch.int32, torch.int64):
                     dist.broadcast(leaf, src=0, group=self.group)
 
-    def _rs_ag_supported(self, hs) -> bool:
-        from sparse_coding_amd.engine.hip_step import HipSAEStep
-
-        return (type(hs) is HipSAEStep and not hs.masked and not hs.reverse
-                and hs.n_dict % max(self.world_size, 1) == 0)
-
     def step(self, local_batch: torch.Tensor):
         if self.world_size == 1 and not self.force_dp_path:
             # single-process: take the ensemble's own step (hipGraph-captured
@@ -210,207 +246,102 @@ class DataParallelEnsembleTrainer:
             return self.ensemble.step_batch(local_batch)
         hs = getattr(self.ensemble, "_hip_step", None)
         if self.dp_mode == "rs_ag":
-            if hs is not None and self._rs_ag_supported(hs):
+            if hs is not None and hs.row_shardable and hs.n_dict % self.world_size == 0:
                 return self._step_rs_ag(hs, local_batch)
             if hs is None and getattr(self.ensemble.optimizer_func, "__name__", "") == "adam":
                 return self._step_rs_ag_torch(local_batch)
-            if not getattr(self, "_rs_ag_warned", False):
+            if not self._rs_ag_warned:
                 print(f"[dp] rs_ag unsupported for {type(hs).__name__}; using allreduce")
                 self._rs_ag_warned = True
         if hs is not None:
-            # fused path: gradient tensors are all-reduced as they become
-            # final (g_bias after k_gc; the [M,n,d] weight grads in model
-            # halves) on a side stream, overlapping the remaining grad GEMMs
-            works = []
-            comm_stream = None
-            if torch.cuda.is_available():
-                if not hasattr(self, "_comm_stream"):
-                    self._comm_stream = torch.cuda.Stream()
-                comm_stream = self._comm_stream
+            return self._step_allreduce(hs, local_batch)
+        return self._step_allreduce_torch(local_batch)
 
-            def on_grads(tensors):
-                if comm_stream is not None:
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    comm_stream.wait_event(ev)
-                    with torch.cuda.stream(comm_stream):
-                        for t in tensors:
-                            works.append((dist.all_reduce(t, async_op=True, group=self.group), t))
-                else:
-                    for t in tensors:
-                        works.append((dist.all_reduce(t, async_op=True, group=self.group), t))
-
-            use_dp = self.world_size > 1 or self.force_dp_path
-
-            def dp_step(x):
-                works.clear()
-                B = hs.grads_phase(x, on_grads=on_grads if use_dp else None)
-                if use_dp:
-                    for w, t in works:
-                        w.wait()
-                    if comm_stream is not None:
-                        torch.cuda.current_stream().wait_stream(comm_stream)
-                    for _, t in works:
-                        t.div_(self.world_size)
-                hs.update_phase(B)
-                return B
-
-            if self.graph_capture and torch.cuda.is_available():
-                B = local_batch.shape[0]
-                # a graph is valid only while the step's workspaces are the
-                # ones it captured: an eager step at a different B reallocates
-                # them (HipSAEStep._alloc), after which replay would write
-                # into freed tensors — identity-check the workspace object
-                # (strong ref held at capture, so the id cannot be reused)
-                if self._graph is not None and hs.codes is not self._graph_ws:
-                    self._graph = None
-                    self._graph_B = None
-                if self._graph is not None and self._graph_B == B:
-                    self._x_static.copy_(local_batch)
-                    self._graph.replay()
-                    return hs._loss_data(B), {"c": hs.codes}
-                if self._dp_steps >= 2 and self._graph is None and self._graph_B != B:
-                    try:
-                        self._x_static = local_batch.contiguous().clone()
-                        torch.cuda.synchronize()
-                        g = torch.cuda.CUDAGraph()
-                        with torch.cuda.graph(g):
-                            dp_step(self._x_static)
-                        self._graph = g
-                        self._graph_B = B
-                        self._graph_ws = hs.codes
-                        self._graph.replay()  # capture does not execute
-                        return hs._loss_data(B), {"c": hs.codes}
-                    except Exception as e:  # noqa: BLE001 - optimization only
-                        print(f"[dp] graph capture failed ({e}); staying eager")
-                        self.graph_capture = False
-                        self._graph = None
-
-            B = dp_step(local_batch)
-            self._dp_steps += 1
-            return hs._loss_data(B), {"c": hs.codes}
-
-        grads, (loss_data, aux) = self.ensemble.compute_grads(local_batch)
+    def _step_allreduce_torch(self, x: torch.Tensor):
+        grads, (loss_data, aux) = self.ensemble.compute_grads(x)
         if self.world_size > 1:
             if self._reducer is None:
-                self._reducer = GradBucketAllReducer(grads, self.bucket_bytes, self.group)
+                self._reducer = GradBucketAllReducer(grads, self.bucket_bytes, self.group, self._overlap)
             self._reducer.all_reduce_(grads)
-        self.ensemble.apply_grads(grads)
+        self.ensemble.apply_grads(grads, aux)
         return loss_data, aux
+
+    def _join_mean(self) -> None:
+        """Join the pending reductions (sums) and turn them into means."""
+        for t in self._overlap.join():
+            t.div_(self.world_size)
+
+    def _step_allreduce(self, hs, x: torch.Tensor):
+        """Fused-step all-reduce: gradient tensors are all-reduced as they
+        become final (g_bias after k_gc; the [M,n,d] weight grads in model
+        quarters) on a side stream, overlapping the remaining grad GEMMs.
+        With graph_capture the whole body, collectives included, replays
+        from a hipGraph."""
+
+        def on_grads(tensors):
+            with self._overlap.side():
+                for t in tensors:
+                    self._overlap.add(dist.all_reduce(t, async_op=True, group=self.group), t)
+
+        def body(xb):
+            B = hs.grads_phase(xb, on_grads=on_grads)
+            self._join_mean()
+            hs.update_phase(B)
+
+        self._replay.run(x, body)
+        return hs._loss_data(x.shape[0]), {"c": hs.codes}
 
     # -- rs_ag (ZeRO-style) ---------------------------------------------------
     def _step_rs_ag(self, hs, x: torch.Tensor):
         """Fused-step rs_ag: weight-grad chunks are reduce-scattered into row
         shards from the on_grads callback (launched on the comm stream so
-        they overlap the remaining grad GEMMs), the renorm-projected Adam
-        (k_project_adam) runs on the LOCAL rows only, and the updated
-        parameter rows are all-gathered.  Bias-sized grads ([M, n] and
-        smaller) are all-reduced and updated everywhere — they are <0.1% of
-        the bytes and the whole-bias L2-decay term does not shard."""
-        import contextlib
-
-        from sparse_coding_amd.engine.hip_step import EPS_NORM
-
-        ens = self.ensemble
-        world = max(self.world_size, 1)
+        they overlap the remaining grad GEMMs), the step's renorm-projected
+        Adam runs on the LOCAL rows only, and the updated parameter rows are
+        all-gathered.  Bias-sized grads ([M, n] and smaller) are all-reduced
+        and updated everywhere — they are <0.1% of the bytes and the
+        whole-bias L2-decay term does not shard."""
+        world = self.world_size
         rank = dist.get_rank(self.group) if (dist.is_initialized() and world > 1) else 0
         d = hs.d_act
-        R = hs.n_models * hs.n_dict
-
-        comm_stream = None
-        if torch.cuda.is_available():
-            if not hasattr(self, "_comm_stream"):
-                self._comm_stream = torch.cuda.Stream()
-            comm_stream = self._comm_stream
-        if not hasattr(self, "_rs_shards"):
-            self._rs_shards = {}
-
-        w_pend = []  # (work|None, grad shard, kind, global row0, chunk rows)
-        b_pend = []  # (work, tensor)
-
-        def locate(t):
-            for kind, base in (("gw", hs.gw), ("gw_enc", getattr(hs, "gw_enc", None))):
-                if base is None:
-                    continue
-                off_b = t.data_ptr() - base.data_ptr()
-                if 0 <= off_b < base.numel() * 4:
-                    return kind, off_b // (4 * d)
-            raise RuntimeError("rs_ag: gradient tensor not in a known workspace")
+        chunks = []  # (update-table entry, gradient shard, first row, rows)
 
         def on_grads(tensors):
-            if comm_stream is not None:
-                ev = torch.cuda.Event()
-                ev.record()
-                comm_stream.wait_event(ev)
-            ctx = torch.cuda.stream(comm_stream) if comm_stream is not None else contextlib.nullcontext()
-            with ctx:
+            with self._overlap.side():
                 for t in tensors:
                     if t.dim() == 2:  # bias-sized
                         if world > 1:
-                            b_pend.append((dist.all_reduce(t, async_op=True, group=self.group), t))
-                    else:
-                        kind, row0 = locate(t)
-                        rows = t.shape[0] * t.shape[1]
-                        k = rows // world
-                        shard = self._rs_shards.get((kind, row0))
-                        if shard is None or shard.shape[0] != k:
-                            shard = torch.empty(k, d, device=t.device, dtype=torch.float32)
-                            self._rs_shards[(kind, row0)] = shard
-                        flat = t.reshape(rows, d)
-                        if world > 1:
-                            work = _reduce_scatter_rows(flat, shard, self.group)
-                        else:  # world-1 force path: same code shape, local copy
-                            shard.copy_(flat)
-                            work = None
-                        w_pend.append((work, shard, kind, row0, rows))
+                            self._overlap.add(dist.all_reduce(t, async_op=True, group=self.group), t)
+                        continue
+                    entry, row0 = hs.locate_grad(t)
+                    rows = t.shape[0] * t.shape[1]
+                    k = rows // world
+                    shard = self._rs_shards.get((entry[0], row0))
+                    if shard is None or shard.shape[0] != k:
+                        shard = torch.empty(k, d, device=t.device, dtype=torch.float32)
+                        self._rs_shards[(entry[0], row0)] = shard
+                    flat = t.reshape(rows, d)
+                    if world > 1:
+                        self._overlap.add(_reduce_scatter_rows(flat, shard, self.group), shard)
+                    else:  # world-1 force path: same code shape, local copy
+                        shard.copy_(flat)
+                    chunks.append((entry, shard, row0, rows))
 
         B = hs.grads_phase(x, on_grads=on_grads)
+        self._join_mean()
 
-        for work, *_ in w_pend:
-            if work is not None:
-                work.wait()
-        for work, _ in b_pend:
-            work.wait()
-        if comm_stream is not None:
-            torch.cuda.current_stream().wait_stream(comm_stream)
-        for _, t in b_pend:
-            t.div_(world)
-
-        st = ens.optim_states
-        st["step"] += 1.0
-        step0 = st["step"].reshape(-1)[0:1]
-        p = ens.params
+        t = hs._begin_update()
         self._rs_consolidate = []
-        norms_flat = hs.norms.reshape(R)
-        lrm_flat = hs.lr_mult.reshape(R)
-        for work, shard, kind, row0, rows in w_pend:
-            if world > 1:
-                shard.div_(world)
+        for (key, _, project), shard, row0, rows in chunks:
             k = rows // world
             g0 = row0 + rank * k
-            if hs.tied:
-                pname, project = "encoder", True
-            elif kind == "gw":
-                pname, project = "decoder", True
-            else:
-                pname, project = "encoder", False
-            Wflat = p[pname].reshape(R, d)
-            mu = st["mu"][pname].reshape(R, d)
-            nu = st["nu"][pname].reshape(R, d)
-            sl = slice(g0, g0 + k)
-            hs.ext.project_adam(Wflat[sl], shard, norms_flat[sl], mu[sl], nu[sl],
-                                step0, k, hs.lr, hs.beta1, hs.beta2, hs.eps,
-                                EPS_NORM, project, lr_mult=lrm_flat[sl])
+            hs._adam_matrix(key, shard, t, project=project, lr_mult=hs.lr_mult, rows=(g0, k))
+            W, mu, nu = hs._param_state(key)
             if world > 1:
-                _all_gather_rows(Wflat[row0 : row0 + rows], Wflat[sl], self.group)
-            self._rs_consolidate.append((st["mu"][pname], row0, rows))
-            self._rs_consolidate.append((st["nu"][pname], row0, rows))
-        # bias params: identical full update on every rank
-        hs.ext.bias_adam(p["encoder_bias"], hs.g_bias, hs.bias_decay,
-                         st["mu"]["encoder_bias"], st["nu"]["encoder_bias"],
-                         st["step"], hs.lr, hs.beta1, hs.beta2, hs.eps,
-                         lr_mult=hs.lr_mult)
-        return hs._loss_data(B), {"c": hs.c}
+                Wflat = W.reshape(-1, d)
+                _all_gather_rows(Wflat[row0 : row0 + rows], Wflat[g0 : g0 + k], self.group)
+            self._rs_consolidate += [(mu, row0, rows), (nu, row0, rows)]
+        hs._update_bias(t)  # bias params: identical full update on every rank
+        return hs._loss_data(B), {"c": hs.codes}
 
     def _step_rs_ag_torch(self, x: torch.Tensor):
         """Generic-tree rs_ag for the torch backend (and the CPU/gloo tests):
@@ -490,12 +421,9 @@ class DataParallelEnsembleTrainer:
         onto every rank.  No-op in allreduce mode or at world 1."""
         if self.dp_mode != "rs_ag" or self.world_size <= 1:
             return
-        ops = getattr(self, "_rs_consolidate", None)
-        if not ops:
-            return
         rank = dist.get_rank(self.group)
         world = self.world_size
-        for mom, row0, rows in ops:
+        for mom, row0, rows in self._rs_consolidate:
             k = rows // world
             d_last = mom.shape[-1]
             flat = mom.reshape(-1, d_last)

@@ -223,6 +223,25 @@ def test_torch_backend_maintains_threshold(case):
     assert torch.isfinite(loss["loss"]).all()
 
 
+def test_torch_dp_path_maintains_threshold(case):
+    """The data-parallel trainer's torch path (compute_grads / apply_grads)
+    runs the buffer hook: after three steps parameters and threshold state
+    equal a twin's stepped with step_batch, bit for bit."""
+    from sparse_coding_amd.parallel.dp import DataParallelEnsembleTrainer
+
+    ens = _ensemble(copy.deepcopy(case["models"]), no_stacking=True)
+    twin = _ensemble(copy.deepcopy(case["models"]), no_stacking=True)
+    trainer = DataParallelEnsembleTrainer(ens, force_dp_path=True)
+    for _ in range(3):
+        trainer.step(case["x"])
+        twin.step_batch(case["x"])
+    assert twin.buffers["threshold_n"].tolist() == [3, 3]
+    for k in ("threshold", "threshold_n"):
+        assert torch.equal(ens.buffers[k], twin.buffers[k]), k
+    for k in twin.params:
+        assert torch.equal(ens.params[k], twin.params[k]), k
+
+
 def test_hook_leaves_other_signatures_alone():
     from sparse_coding_amd.models.sae_signatures import FunctionalTiedSAE
     from sparse_coding_amd.models.topk import TopKEncoder
@@ -346,10 +365,15 @@ def test_step_reads_threshold_state_at_launch_time():
     """A resumed sweep replaces ens.buffers: the next launch must see the new
     tensors, and a captured graph holding the old addresses must go."""
     ens, step, ext, _ = _traced_step()
-    step._graph, step._captured_state = object(), step._state_ptrs()
+    replay = step._replay
+    replay.enabled = True
+    replay._check_key()  # the key a capture at this point would be tied to
+    replay.graph, held = object(), step.graph_key()
     ens.buffers = {k: v.clone() for k, v in ens.buffers.items()}
-    assert step._captured_state != step._state_ptrs()
-    step.use_graph = False  # CPU: only the invalidation is under test
+    assert held != step.graph_key() and held[0] is step.graph_key()[0]
+    replay._check_key()
+    assert step._graph is None
+    step.use_graph = False  # CPU: the launch below runs eagerly
     ext.calls.clear()
     step.step(ext.x)
     assert step._graph is None

@@ -556,6 +556,96 @@ def test_dp_rccl_graph_capture_one_rank():
         dist.destroy_process_group()
 
 
+def _one_rank_dp_graph_pair(sig, models, port):
+    """A one-rank nccl group, a graph-capturing forced-path trainer over a
+    fused ensemble, and a twin ensemble to step with step_batch."""
+    import os
+
+    import torch.distributed as dist
+
+    from sparse_coding_amd.engine.ensemble import FunctionalEnsemble
+    from sparse_coding_amd.functional.optim import adam
+    from sparse_coding_amd.parallel.dp import DataParallelEnsembleTrainer
+
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("nccl", rank=0, world_size=1)
+    ens = FunctionalEnsemble(models, sig, adam, {"lr": 1e-3}, device=DEV, backend="hip")
+    models2 = [({k: v.clone() for k, v in p.items()}, {k: v.clone() for k, v in b.items()})
+               for p, b in ens.unstack()]
+    twin = FunctionalEnsemble(models2, sig, adam, {"lr": 1e-3}, device=DEV, backend="hip")
+    return DataParallelEnsembleTrainer(ens, force_dp_path=True, graph_capture=True), ens, twin
+
+
+def test_dp_graph_across_a_batch_size_change():
+    """The DP graph over a tied step through 256 x4, 132 x4, 256 x4: 132 is
+    ragged against the 128-row tile and reallocates the workspaces, so each
+    stretch is two eager steps, a capture and replays."""
+    import torch.distributed as dist
+
+    from sparse_coding_amd.models.sae_signatures import FunctionalTiedSAE
+
+    torch.manual_seed(35)
+    M, d, n = 2, 64, 256
+    models = [FunctionalTiedSAE.init(d, n, 1e-3, device=DEV) for _ in range(M)]
+    try:
+        trainer, ens, twin = _one_rank_dp_graph_pair(FunctionalTiedSAE, models, 29573)
+        for B in (256, 132, 256):
+            x = torch.randn(B, d, device=DEV)
+            for _ in range(4):
+                losses, _ = trainer.step(x)
+                twin.step_batch(x)
+            assert trainer._graph is not None, f"no graph after four steps at B={B}"
+        torch.cuda.synchronize()
+        assert torch.isfinite(losses["loss"]).all()
+        for k in twin.params:
+            err = (ens.params[k] - twin.params[k]).abs().max().item()
+            assert err < 1e-6, (k, err)
+    finally:
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def test_dp_graph_follows_a_replaced_batch_topk_buffer_tree():
+    """A resumed sweep replaces ens.buffers: the DP graph over a BatchTopK
+    step is dropped with the step's own, the new threshold state is updated
+    and the old tensors are no longer written."""
+    import torch.distributed as dist
+
+    from sparse_coding_amd.models.batch_topk import BatchTopKEncoder
+
+    torch.manual_seed(36)
+    M, B, d, n, k = 2, 256, 64, 256, 8
+    models = [BatchTopKEncoder.init(d, n, k) for _ in range(M)]
+    try:
+        trainer, ens, twin = _one_rank_dp_graph_pair(BatchTopKEncoder, models, 29574)
+        x = torch.randn(B, d, device=DEV)
+        for _ in range(3):
+            trainer.step(x)
+            twin.step_batch(x)
+        assert trainer._graph is not None, "graph capture did not engage"
+        old = ens.buffers
+        ens.buffers = {key: v.clone() for key, v in old.items()}
+        torch.cuda.synchronize()
+        frozen = {key: v.clone() for key, v in old.items()}
+        for _ in range(3):
+            trainer.step(x)
+            twin.step_batch(x)
+        torch.cuda.synchronize()
+        assert trainer._graph is not None
+        for key, v in frozen.items():
+            assert torch.equal(old[key], v), f"old buffer {key} was written"
+        assert ens.buffers["threshold_n"].tolist() == twin.buffers["threshold_n"].tolist() == [6, 6]
+        err = (ens.buffers["threshold"] - twin.buffers["threshold"]).abs().max().item()
+        assert err < 1e-6, ("threshold", err)
+        for key in twin.params:
+            err = (ens.params[key] - twin.params[key]).abs().max().item()
+            assert err < 1e-6, (key, err)
+    finally:
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+
 def test_lr_mult_freezes_rows():
     """k_project_adam/k_bias_adam per-row lr multiplier: rows at 0 must not
     move; rows at 1 must match a run without lr_mult."""
