@@ -63,6 +63,7 @@ overlaps with nothing locally but lands between grad GEMMs and Adam.
 
 from __future__ import annotations
 
+import gc
 import os
 from typing import Optional
 
@@ -172,10 +173,17 @@ class GraphReplay:
             self._key = key
 
     def _capture(self, x, body):
+        # No cyclic garbage collection while the stream is capturing: a
+        # collection that starts inside the body may finalize GPU objects of
+        # earlier owners (graphs, events, communicators), and releasing those
+        # is not allowed during a capture; the runtime aborts the process.
+        # torch.cuda.graph collects once itself before the capture begins.
+        gc_was_on = gc.isenabled()
         try:
             self.x_static = x.clone()
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
+            gc.disable()
             with torch.cuda.graph(g):
                 body(self.x_static)
             self.graph = g
@@ -183,6 +191,9 @@ class GraphReplay:
             print(f"{self.what} failed ({e}); staying eager")
             self.enabled = False
             self.graph = None
+        finally:
+            if gc_was_on:
+                gc.enable()
 
     def run(self, x: torch.Tensor, body) -> None:
         """body(x), eagerly or as a replay of its capture."""

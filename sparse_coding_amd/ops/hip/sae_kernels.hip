@@ -32,7 +32,14 @@
 //    that); k_dec_fwd_t<16> would spill there and stays at (512,6).
 //  * ping-pong LDS double buffer + register prefetch (guide T14/G15): ONE
 //    barrier per K-step; the NEXT K-tile's global loads issue before the
-//    MFMA phase of the current tile.
+//    MFMA phase of the current tile and are waited for (counted vmcnt) after
+//    its last MFMA, in front of the LDS writes.  In the ALIGNED variants the
+//    compiler does not keep that order by itself; gemm_mainloop says what pins
+//    it, tests/test_codeobject_schedule.py checks every aligned variant's
+//    loop in the built code object (table: profiles/README.md, r07).  The
+//    guarded variants wait vmcnt(0) for their (conditional) loads before the
+//    writes; the fragment reads of the MFMA phase are just-in-time (ds_read,
+//    lgkmcnt(0), 2 MFMAs) in every variant.
 //  * LDS staging is conflict-free: transposed tiles use stride BM+1 (b32
 //    writes); direct tiles use stride BM with float4 (b128) writes.
 //  * optional s_setprio(1) on the second-dispatched wave half (runtime
@@ -141,7 +148,6 @@ struct TLds {
 template <int TBK, int TROWS = BM, bool ALIGNED = false>
 __device__ __forceinline__ void stage_T_load(const float* __restrict__ src, long ld,
                                              int i0, int k0, int n_rows, int n_k,
-                                             const float* __restrict__ scale,
                                              TStage<TBK, TROWS>& st) {
   const int t = threadIdx.x;
   constexpr int TPR = TBK / 4;                 // threads covering one row's K
@@ -152,10 +158,8 @@ __device__ __forceinline__ void stage_T_load(const float* __restrict__ src, long
     int kc = (t % TPR) * 4;
     int gi = i0 + i;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    float sc = 1.f;
     if constexpr (ALIGNED) {
       v = *reinterpret_cast<const float4*>(src + (long)gi * ld + k0 + kc);
-      if (scale) sc = scale[gi];
     } else if (gi < n_rows) {
       const float* row = src + (long)gi * ld + k0 + kc;
       if (k0 + kc + 3 < n_k) {
@@ -165,10 +169,23 @@ __device__ __forceinline__ void stage_T_load(const float* __restrict__ src, long
         for (int s = 0; s < 4; ++s)
           if (k0 + kc + s < n_k) ((float*)&v)[s] = row[s];
       }
-      if (scale) sc = scale[gi];
     }
     st.v[p] = v;
-    st.sc[p] = sc;
+  }
+}
+
+// The scale of a transposed tile belongs to its row, not to the K-tile, so it
+// is loaded once, ahead of the K-loop (1 where there is no scale or no row).
+// Loaded with every tile, it sat at the top of the unguarded gc kernels' MFMA
+// phase with a vmcnt(0) behind it that also waited for the tile loads.
+template <int TBK, int TROWS, bool ALIGNED>
+__device__ __forceinline__ void stage_T_scale(const float* __restrict__ scale, int i0, int n_rows,
+                                              TStage<TBK, TROWS>& st) {
+  constexpr int RPP = NTHREADS / (TBK / 4);
+#pragma unroll
+  for (int p = 0; p < TBK * TROWS / 2048; ++p) {
+    int gi = i0 + p * RPP + threadIdx.x / (TBK / 4);
+    st.sc[p] = (scale && (ALIGNED || gi < n_rows)) ? scale[gi] : 1.f;
   }
 }
 
@@ -291,6 +308,28 @@ __device__ __forceinline__ void mfma_tile(const float* __restrict__ As,
 // write_a/write_b(buf) store those registers into LDS buffer `buf`.
 // k_gc_t holds a written-out copy of this loop (the reason is stated there):
 // a change to the order of operations here has to be made there too.
+//
+// The order above is the source's; two things pin it in the code object
+// (tests/test_codeobject_schedule.py reads it back from the disassembly):
+//  * kloop_loads_issued(): an unguarded load of a `const __restrict__` kernel
+//    argument is a load of constant memory to the compiler, free of any
+//    ordering, and instruction selection sinks it to its first use: behind the
+//    MFMA phase, straight in front of its own s_waitcnt.  The staged operands
+//    of the GEMM kernels are therefore NOT declared __restrict__, and the
+//    compiler-only memory fence after the loads keeps them ahead of the LDS
+//    reads of the MFMA phase.  Either alone changes nothing.  It is the
+//    qualifier on the KERNEL's arguments that matters: the `__restrict__` on
+//    the `src` parameter of stage_T_load / stage_D_load is inlined away and
+//    does no harm; do not put it back on the kernels to match.
+//  * kloop_mfma_issued(): a scheduling barrier between the MFMA phase and the
+//    LDS writes.  Without it the scheduler pulls the writes' scale multiplies
+//    in among the first MFMAs, and the s_waitcnt vmcnt they need with them.
+//    Mask 0x8: MFMAs alone may cross it, so the last one or two still run
+//    behind the writes and the workgroup barrier (with mask 0 the TBK=32
+//    k_dec_fwd_t measured 10 us slower; profiles/README.md, r07).
+__device__ __forceinline__ void kloop_loads_issued() { asm volatile("" ::: "memory"); }
+__device__ __forceinline__ void kloop_mfma_issued() { __builtin_amdgcn_sched_barrier(0x8); }
+
 template <int TBK, int NACC, class ALds, class BLds, class LoadA, class LoadB, class WriteA,
           class WriteB>
 __device__ __forceinline__ void gemm_mainloop(int k_total, ALds& As, BLds& Bs, f32x16 (&acc)[NACC],
@@ -306,7 +345,9 @@ __device__ __forceinline__ void gemm_mainloop(int k_total, ALds& As, BLds& Bs, f
   for (int k0 = TBK; k0 < k_total; k0 += TBK) {
     load_a(k0);
     load_b(k0);
+    kloop_loads_issued();
     mfma_tile<TBK, NACC, ASTR, BSTR>(As.buf[cur], Bs.buf[cur], acc);
+    kloop_mfma_issued();
     write_a(cur ^ 1);
     write_b(cur ^ 1);
     __syncthreads();
@@ -505,8 +546,8 @@ __device__ __forceinline__ float gate_gp(float u) {  // dg/du (0 at the kinks)
 // ---------------------------------------------------------------------------
 template <int TBK, int MINW, int TBN = BN, bool ALIGNED = false>
 __global__ __launch_bounds__(NTHREADS, MINW)
-void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
-                 const float* __restrict__ Wenc,    // [M, n, d]
+void k_enc_fwd_t(const float* x,                    // [B, d]     (staged operands: no
+                 const float* Wenc,                 // [M, n, d]   __restrict__, see gemm_mainloop)
                  const float* __restrict__ bias,    // [M, n]
                  const float* __restrict__ inv_norms, // [M, n] or nullptr
                  float* __restrict__ c_out,         // [M, B, n]
@@ -538,10 +579,11 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
 
   TStage<TBK, BM> sa;
   TStage<TBK, TBN> sb;
+  stage_T_scale<TBK, TBN, ALIGNED>(inv, t.col0, n, sb);
   gemm_mainloop<TBK>(
       d, As, Bs, t.acc,
-      [&](int k0) { stage_T_load<TBK, BM, ALIGNED>(x_m, d, t.row0, k0, B, d, nullptr, sa); },
-      [&](int k0) { stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, k0, n, d, inv, sb); },
+      [&](int k0) { stage_T_load<TBK, BM, ALIGNED>(x_m, d, t.row0, k0, B, d, sa); },
+      [&](int k0) { stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, k0, n, d, sb); },
       [&](int buf) { stage_T_write(sa, As, buf, false); },
       [&](int buf) { stage_T_write(sb, Bs, buf, scaled); });
 
@@ -658,8 +700,8 @@ void k_enc_fwd_t(const float* __restrict__ x,       // [B, d]
 // ---------------------------------------------------------------------------
 template <int TBK, int MINW, int TBN = BN, bool ALIGNED = false>
 __global__ __launch_bounds__(NTHREADS, MINW)
-void k_dec_fwd_t(const float* __restrict__ c,       // [M, B, n]
-                 const float* __restrict__ Wdec,    // [M, n, d]
+void k_dec_fwd_t(const float* c,                    // [M, B, n]  (staged operands: no
+                 const float* Wdec,                 // [M, n, d]   __restrict__, see gemm_mainloop)
                  const float* __restrict__ inv_norms, // [M, n]
                  const float* __restrict__ x,       // [B, d]
                  float* __restrict__ r_out,         // [M, B, d]
@@ -681,7 +723,7 @@ void k_dec_fwd_t(const float* __restrict__ c,       // [M, B, n]
   DStage<TBK, TBN> sb;
   gemm_mainloop<TBK>(
       n, As, Bs, t.acc,
-      [&](int k0) { stage_T_load<TBK, BM, ALIGNED>(c_m, n, t.row0, k0, B, n, nullptr, sa); },
+      [&](int k0) { stage_T_load<TBK, BM, ALIGNED>(c_m, n, t.row0, k0, B, n, sa); },
       [&](int k0) { stage_D_load<TBK, TBN, ALIGNED>(W, d, k0, t.col0, n, d, inv, sb); },
       [&](int buf) { stage_T_write(sa, As, buf, false); },
       [&](int buf) { stage_D_write(sb, Bs, buf, true); });
@@ -708,8 +750,8 @@ void k_dec_fwd_t(const float* __restrict__ c,       // [M, B, n]
 // ---------------------------------------------------------------------------
 template <int TBK, int MINW, int TBN = BN, bool ALIGNED = false>
 __global__ __launch_bounds__(NTHREADS, MINW)
-void k_gc_t(const float* __restrict__ r,        // [M, B, d]
-            const float* __restrict__ Wdec,     // [M, n, d]
+void k_gc_t(const float* r,                     // [M, B, d]  (staged operands: no
+            const float* Wdec,                  // [M, n, d]   __restrict__, see gemm_mainloop)
             const float* __restrict__ inv_norms,// [M, n]
             const float* __restrict__ c,        // [M, B, n]
             const float* __restrict__ l1_alpha, // [M]
@@ -734,20 +776,23 @@ void k_gc_t(const float* __restrict__ r,        // [M, B, d]
   // This kernel alone writes gemm_mainloop's loop and the epilogue walk out.
   // Through the helpers its aligned <16, 8, 128> variant is scheduled
   // differently (and with epi_cols/epi_rows takes 64 VGPRs, not 63) and
-  // measured 0.4-0.7% slower; written out it compiles to the instruction
-  // stream it had before the helpers existed (profiles/README.md, r04).
+  // measured 0.4-0.7% slower (profiles/README.md, r04; that was before the
+  // K-loop's order was pinned in r07 and has not been measured again since).
   {
     constexpr int ASTR = TLds<TBK, BM>::STRIDE, BSTR = TLds<TBK, TBN>::STRIDE;
     int cur = 0;
-    stage_T_load<TBK, BM, ALIGNED>(r_m, d, t.row0, 0, B, d, nullptr, sa);
-    stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, 0, n, d, inv, sb);
+    stage_T_scale<TBK, TBN, ALIGNED>(inv, t.col0, n, sb);
+    stage_T_load<TBK, BM, ALIGNED>(r_m, d, t.row0, 0, B, d, sa);
+    stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, 0, n, d, sb);
     stage_T_write(sa, As, 0, false);
     stage_T_write(sb, Bs, 0, true);
     __syncthreads();
     for (int k0 = TBK; k0 < d; k0 += TBK) {
-      stage_T_load<TBK, BM, ALIGNED>(r_m, d, t.row0, k0, B, d, nullptr, sa);
-      stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, k0, n, d, inv, sb);
+      stage_T_load<TBK, BM, ALIGNED>(r_m, d, t.row0, k0, B, d, sa);
+      stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, k0, n, d, sb);
+      kloop_loads_issued();
       mfma_tile<TBK, NACC, ASTR, BSTR>(As.buf[cur], Bs.buf[cur], t.acc);
+      kloop_mfma_issued();
       stage_T_write(sa, As, cur ^ 1, false);
       stage_T_write(sb, Bs, cur ^ 1, true);
       __syncthreads();
@@ -838,8 +883,8 @@ void k_colsum_groups(const float* __restrict__ part,  // [M, nrg, n]
 // ---------------------------------------------------------------------------
 template <int TBK, int MINW, int TBN = BN, bool ALIGNED = false>
 __global__ __launch_bounds__(NTHREADS, MINW)
-void k_gc_thresh_t(const float* __restrict__ r,        // [M, B, d]
-                   const float* __restrict__ Wdec,     // [M, n, d]
+void k_gc_thresh_t(const float* r,                     // [M, B, d]  (staged operands: no
+                   const float* Wdec,                  // [M, n, d]   __restrict__, see gemm_mainloop)
                    const float* __restrict__ inv_norms,// [M, n]
                    const float* __restrict__ c,        // [M, B, n] (codes)
                    const float* __restrict__ u,        // [M, B, n]
@@ -865,10 +910,11 @@ void k_gc_thresh_t(const float* __restrict__ r,        // [M, B, d]
 
   TStage<TBK, BM> sa;
   TStage<TBK, TBN> sb;
+  stage_T_scale<TBK, TBN, ALIGNED>(inv, t.col0, n, sb);
   gemm_mainloop<TBK>(
       d, As, Bs, t.acc,
-      [&](int k0) { stage_T_load<TBK, BM, ALIGNED>(r_m, d, t.row0, k0, B, d, nullptr, sa); },
-      [&](int k0) { stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, k0, n, d, inv, sb); },
+      [&](int k0) { stage_T_load<TBK, BM, ALIGNED>(r_m, d, t.row0, k0, B, d, sa); },
+      [&](int k0) { stage_T_load<TBK, TBN, ALIGNED>(W, d, t.col0, k0, n, d, sb); },
       [&](int buf) { stage_T_write(sa, As, buf, false); },
       [&](int buf) { stage_T_write(sb, Bs, buf, true); });
 
@@ -1326,8 +1372,8 @@ void k_btk_write(const float* __restrict__ scores,  // [M, B, n]
 // ---------------------------------------------------------------------------
 template <int TBK, int MINW, int TBN = BN, bool ALIGNED = false>
 __global__ __launch_bounds__(NTHREADS, MINW)
-void k_grad_w_t(const float* __restrict__ P, long p_batch_stride,
-                const float* __restrict__ Q, long q_batch_stride,
+void k_grad_w_t(const float* P, long p_batch_stride,  // staged operands: no __restrict__,
+                const float* Q, long q_batch_stride,  // see gemm_mainloop
                 float* __restrict__ gw,  // [M, n, d]
                 float alpha, float beta,
                 int B, int n, int d, int prio) {
