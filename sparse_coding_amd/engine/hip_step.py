@@ -784,6 +784,12 @@ class HipLISTAStep(_HipStep):
     def __init__(self, ensemble, ext):
         super().__init__(ensemble, ext)
         self.n_layers = len(ensemble.params["encoder_layers"])
+        # rho's Adam runs as torch ops.  The Adam kernels receive the betas as
+        # fp32 and form 1 - beta exactly; the same two values here, so that
+        # every parameter of the step runs one recurrence (1 - 0.999 rounded to
+        # fp32 on its own is 4.7e-5 off 1 - fp32(0.999), which the bias
+        # correction 1 - beta^t does not undo)
+        self._b1, self._b2 = (torch.tensor(b, dtype=torch.float32).item() for b in (self.beta1, self.beta2))
 
     @property
     def codes(self):
@@ -894,10 +900,11 @@ class HipLISTAStep(_HipStep):
         rho, mu, nu = self._param_state(("encoder_layers", l, "rho"))
         g = self.g_rho[l].reshape(rho.shape)
         t = step_no.reshape(rho.shape)
-        mu.mul_(self.beta1).add_(g, alpha=1 - self.beta1)
-        nu.mul_(self.beta2).addcmul_(g, g, value=1 - self.beta2)
-        bc1 = 1 - torch.pow(self.beta1, t)
-        bc2 = 1 - torch.pow(self.beta2, t)
+        b1, b2 = self._b1, self._b2
+        mu.mul_(b1).add_(g, alpha=1 - b1)
+        nu.mul_(b2).addcmul_(g, g, value=1 - b2)
+        bc1 = 1 - torch.pow(b1, t)
+        bc2 = 1 - torch.pow(b2, t)
         rho.sub_(self.lr * (mu / bc1) / ((nu / bc2).sqrt() + self.eps))
 
     def _loss_data(self, B: int):
@@ -1038,7 +1045,8 @@ class HipSemilinearStep(_HipStep):
         M, n, d, h = self.n_models, self.n_dict, self.d_act, self.hidden
         f = self._empty
         self.norms, self.inv_norms = f(M, n), f(M, n)
-        self.ones_mh = self._ones(M, h)
+        # unit row scales for the g_c W2 product: one per row of W2 [M, n, h]
+        self.ones_mn = self._ones(M, n)
         self.zeros_bh = self._zeros(B, h)
         self.scratch_lp = f(M, 2)
         self.loss_parts = f(M, 2)
@@ -1084,7 +1092,7 @@ class HipSemilinearStep(_HipStep):
         ext.grad_w(self.c, self.rr, self.gA, gscale, 0.0, bk_gw, prio)
         ext.grad_w(self.g_c, self.h1, self.gW2, 1.0, 0.0, bk_gw, prio)
         # g_h1 = (g_c W2) * [h1 > 0]
-        ext.dec_fwd(self.g_c, l2p["weight"], self.ones_mh, self.zeros_bh,
+        ext.dec_fwd(self.g_c, l2p["weight"], self.ones_mn, self.zeros_bh,
                     self.g_h, self.scratch_lp, bk_dec, prio)
         self.g_h.mul_((self.h1 > 0).float())
         # strided-reduce -> k_colsum (9% of the semilinear step,
