@@ -20,6 +20,8 @@ hand-written gfx950 HIP kernels (``sparse_coding_amd/ops/hip/sae_kernels.hip``):
                    decoder renormalization) + fused Adam; optional separate
                    "used" weights + clamp-derivative mask (positive SAE)
   k_bias_adam    : Adam on any [M,k] vector param (+ L2-decay gradient)
+  k_sparse_dec_gc/k_sparse_grad_w : the TopK family's decode, code-grad and
+                   weight-grad over the hits c > 0 alone (topk_chain="sparse")
   k_topk_select  : per-row radix top-k + scatter (TopK)
   k_btk_hist/k_btk_write : batch-level radix top-k over many workgroups +
                    scatter + inference-threshold state (BatchTopK)
@@ -1124,6 +1126,15 @@ class HipTopKStep(_HipStep):
     term, and the dictionary normalization has NO eps clamp
     (reference topk_encoder.py:31).  The per-model k lives in
     buffers["sparsity"]; selection runs in one kernel (k_topk_select).
+
+    What follows the selection is the kernel config's ``topk_chain``,
+    resolved once per workspace allocation like ``staging``.  "dense" (the
+    default) runs dec_fwd, gc and two grad_w GEMMs over the whole [M, B, n]
+    code matrix.  "sparse" runs k_sparse_dec_gc and k_sparse_grad_w, which
+    visit only the hits ``c > 0`` of the same dense ``c`` and produce the same
+    ``r``, ``loss_parts[:, 0]`` and ``gw``; codes, fired counts, the
+    announced gradient and graph capture are the dense chain's.  It serves
+    d <= ext.sparse_max_d() and raises at allocation beyond that.
     """
 
     EPS = 1e-30  # un-clamped normalization (reference divides by the raw norm)
@@ -1143,14 +1154,26 @@ class HipTopKStep(_HipStep):
         f = self._empty
         self.scores = f(M, B, n)
         self.c = f(M, B, n)
+        # the sparse chain writes gpre at the hits c > 0 only; every other
+        # element of the buffer is unspecified there
         self.gpre = f(M, B, n)
         self.r = f(M, B, d)
         self.norms = f(M, n)
         self.inv_norms = f(M, n)
         self.loss_parts = f(M, 2)
         self.fired = self._zeros(M, n)
-        self.g_bias_scratch = f(M, n)
         self.gw = f(M, n, d)
+        if self.kc["topk_chain"] == "sparse":
+            if d > self.ext.sparse_max_d():
+                raise RuntimeError(f"topk_chain='sparse' serves d <= {self.ext.sparse_max_d()}, got d = {d}")
+            # per feature the ascending list of its hit rows, stride B (its
+            # worst case).  It lives in the bytes of `scores`, which are dead
+            # once the selection has written c and hold exactly M*n*B int32.
+            assert self.ext.sparse_hits_size(M, B, n) == self.scores.numel()
+            self.hits = self.scores.view(torch.int32).view(M, n, B)
+            self.hit_counts = torch.empty(M, n, device=self._dev, dtype=torch.int32)
+        else:
+            self.g_bias_scratch = f(M, n)
 
     def _grads(self, x, B, on_grads):
         ext, bk, prio, bk_gw = self.ext, self.bk, self.prio, self.bk_gw
@@ -1162,6 +1185,11 @@ class HipTopKStep(_HipStep):
                     self.scores, self.loss_parts, self.fired, 1, bk, prio)
         self._select()
 
+        if self.kc["topk_chain"] == "sparse":
+            ext.sparse_dec_gc(self.c, W, self.inv_norms, x, self.r, self.gpre, self.loss_parts)
+            ext.sparse_grad_w(self.c, self.gpre, self.r, x, self.gw, self.hits, self.hit_counts)
+            _announce(on_grads, self.gw)
+            return
         ext.dec_fwd(self.c, W, self.inv_norms, x, self.r, self.loss_parts, self.bk_dec, prio)
         ext.gc(self.r, W, self.inv_norms, self.c, self.zero_l1,
                self.gpre, self.g_bias_scratch, bk, prio, accumulate=False)
@@ -1198,7 +1226,10 @@ class HipBatchTopKStep(HipTopKStep):
     no host read, K computed on the device, captured in the step's hipGraph
     with the rest of the chain.  The write pass also reports the batch's
     selection threshold (``thr_batch``, returned as loss_data["threshold"])
-    and folds it into the inference-threshold state.
+    and folds it into the inference-threshold state.  Everything behind the
+    selection, the ``topk_chain`` choice included, is HipTopKStep's: the
+    sparse kernels define a hit as ``c > 0`` and never read k, so a row or a
+    column with any number of hits is served.
 
     That state (buffers "threshold", "threshold_n", "threshold_lr") is read
     from ``ens.buffers`` at every launch, not at construction: a resumed

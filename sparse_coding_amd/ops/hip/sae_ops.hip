@@ -431,6 +431,90 @@ void batch_topk_select(torch::Tensor scores, torch::Tensor c_out, torch::Tensor 
                      th_p, thn_p, thlr_p, (int)B, (int)n);
 }
 
+// The sparse TopK chain (k_sparse_dec_gc / k_sparse_grad_w).  Both kernels are
+// templates over DL, the registers a lane holds of one length-d vector; the
+// launchers take the smallest compiled DL >= ceil(d / 64).  The second template
+// argument is the kernel's minimum waves per SIMD.
+int64_t sparse_max_d() { return SPARSE_MAX_D; }
+
+// int32 elements of the hit-list workspace sparse_grad_w needs: [M, n, B]
+int64_t sparse_hits_size(int64_t M, int64_t B, int64_t n) { return M * n * B; }
+
+#define SPARSE_DISPATCH_DL(d, LAUNCH)                                        \
+  do {                                                                        \
+    const int dl_ = cdiv(d, WAVE);                                            \
+    if (dl_ <= 1) LAUNCH(1);                                                  \
+    else if (dl_ <= 2) LAUNCH(2);                                             \
+    else if (dl_ <= 4) LAUNCH(4);                                             \
+    else if (dl_ <= 8) LAUNCH(8);                                             \
+    else if (dl_ <= 12) LAUNCH(12);                                           \
+    else if (dl_ <= 16) LAUNCH(16);                                           \
+    else LAUNCH(32);                                                          \
+  } while (0)
+
+struct SparseShape {
+  int M, B, n, d;
+  long x_mstride;
+};
+
+// shapes shared by the two launchers: c [M, B, n], r [M, B, d], x [B, d] or [M, B, d]
+static SparseShape sparse_shape(const char* who, const torch::Tensor& c, const torch::Tensor& gpre,
+                                const torch::Tensor& r, const torch::Tensor& x) {
+  TORCH_CHECK(c.dim() == 3 && r.dim() == 3, who, ": c must be [M,B,n] and r [M,B,d]");
+  const long M = c.size(0), B = c.size(1), n = c.size(2), d = r.size(2);
+  TORCH_CHECK(d >= 1 && d <= SPARSE_MAX_D, who, ": d = ", d, " is outside the sparse chain's range 1..",
+              SPARSE_MAX_D);
+  TORCH_CHECK(gpre.sizes() == c.sizes(), who, ": gpre must have the shape of c");
+  TORCH_CHECK(r.size(0) == M && r.size(1) == B, who, ": r must be [M,B,d]");
+  TORCH_CHECK(x.size(-1) == d && x.size(x.dim() - 2) == B && (x.dim() == 2 || x.dim() == 3),
+              who, ": x must be [B,d] or [M,B,d]");
+  TORCH_CHECK(M <= 65535 && B < (1L << 31) && n < (1L << 31), who, ": M, B or n too large");
+  return {(int)M, (int)B, (int)n, (int)d, x_model_stride(x, (int)M)};
+}
+
+void sparse_dec_gc(torch::Tensor c, torch::Tensor W, torch::Tensor inv_norms, torch::Tensor x,
+                   torch::Tensor r, torch::Tensor gpre, torch::Tensor loss_parts) {
+  CHECK_IN(c); CHECK_IN(W); CHECK_IN(inv_norms); CHECK_IN(x); CHECK_IN(r); CHECK_IN(gpre);
+  CHECK_IN(loss_parts);
+  const SparseShape s = sparse_shape("sparse_dec_gc", c, gpre, r, x);
+  TORCH_CHECK(W.dim() == 3 && W.size(0) == s.M && W.size(1) == s.n && W.size(2) == s.d,
+              "sparse_dec_gc: W must be [M,n,d]");
+  TORCH_CHECK(inv_norms.numel() == (long)s.M * s.n, "sparse_dec_gc: inv_norms must be [M,n]");
+  TORCH_CHECK(loss_parts.numel() == (long)s.M * 2, "sparse_dec_gc: loss_parts must be [M,2]");
+  if (s.M == 0 || s.B == 0) return;
+  dim3 grid(cdiv(s.B, SDG_T / WAVE), s.M);
+#define LAUNCH_SDG(DL)                                                                        \
+  hipLaunchKernelGGL((k_sparse_dec_gc<DL, (DL <= 16 ? 8 : 2)>), grid, dim3(SDG_T), 0,         \
+                     cur_stream(), c.data_ptr<float>(), W.data_ptr<float>(),                  \
+                     inv_norms.data_ptr<float>(), x.data_ptr<float>(), r.data_ptr<float>(),   \
+                     gpre.data_ptr<float>(), loss_parts.data_ptr<float>(), s.B, s.d, s.n,     \
+                     s.x_mstride)
+  SPARSE_DISPATCH_DL(s.d, LAUNCH_SDG);
+#undef LAUNCH_SDG
+}
+
+void sparse_grad_w(torch::Tensor c, torch::Tensor gpre, torch::Tensor r, torch::Tensor x,
+                   torch::Tensor gw, torch::Tensor hits, torch::Tensor hit_counts) {
+  CHECK_IN(c); CHECK_IN(gpre); CHECK_IN(r); CHECK_IN(x); CHECK_IN(gw);
+  const SparseShape s = sparse_shape("sparse_grad_w", c, gpre, r, x);
+  TORCH_CHECK(gw.dim() == 3 && gw.size(0) == s.M && gw.size(1) == s.n && gw.size(2) == s.d,
+              "sparse_grad_w: gw must be [M,n,d]");
+  TORCH_CHECK(hits.numel() >= sparse_hits_size(s.M, s.B, s.n),
+              "sparse_grad_w: hits needs sparse_hits_size(M, B, n) int32 elements");
+  TORCH_CHECK(hit_counts.numel() == (long)s.M * s.n, "sparse_grad_w: hit_counts must be [M,n]");
+  int* hits_p = int32_ptr(hits, "hits");
+  int* counts_p = int32_ptr(hit_counts, "hit_counts");
+  if (s.M == 0 || s.n == 0) return;
+  dim3 grid(cdiv(s.n, SGW_STRIP), s.M);
+#define LAUNCH_SGW(DL)                                                                        \
+  hipLaunchKernelGGL((k_sparse_grad_w<DL, (DL <= 16 ? 4 : 2)>), grid, dim3(SGW_T), 0,         \
+                     cur_stream(), c.data_ptr<float>(), gpre.data_ptr<float>(),               \
+                     r.data_ptr<float>(), x.data_ptr<float>(), gw.data_ptr<float>(), hits_p,  \
+                     counts_p, s.B, s.d, s.n, s.x_mstride)
+  SPARSE_DISPATCH_DL(s.d, LAUNCH_SGW);
+#undef LAUNCH_SGW
+}
+
 void resample(torch::Tensor fired, torch::Tensor new_rows, torch::Tensor enc_scale,
               torch::Tensor W, torch::Tensor mu_w, torch::Tensor nu_w,
               c10::optional<torch::Tensor> dec,
@@ -516,6 +600,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("thr_out"), py::arg("work"),
         py::arg("threshold") = py::none(), py::arg("threshold_n") = py::none(),
         py::arg("threshold_lr") = py::none());
+  m.def("sparse_max_d", &sparse_max_d, "largest d the sparse TopK chain serves");
+  m.def("sparse_hits_size", &sparse_hits_size, "int32 elements of sparse_grad_w's hit-list workspace",
+        py::arg("M"), py::arg("B"), py::arg("n"));
+  m.def("sparse_dec_gc", &sparse_dec_gc,
+        "TopK chain over the hits c > 0: r = c @ What - x (+MSE partial), gpre at the hits only",
+        py::arg("c"), py::arg("W"), py::arg("inv_norms"), py::arg("x"), py::arg("r"),
+        py::arg("gpre"), py::arg("loss_parts"));
+  m.def("sparse_grad_w", &sparse_grad_w,
+        "gw[j,:] = sum over the hit rows of gscale c r + gpre x; no atomics, every row written",
+        py::arg("c"), py::arg("gpre"), py::arg("r"), py::arg("x"), py::arg("gw"),
+        py::arg("hits"), py::arg("hit_counts"));
   m.def("resample", &resample, "fused dead-neuron resample (K14): rank dead, rewrite rows, zero Adam state",
         py::arg("fired"), py::arg("new_rows"), py::arg("enc_scale"),
         py::arg("W"), py::arg("mu_w"), py::arg("nu_w"),

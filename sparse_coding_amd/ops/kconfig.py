@@ -27,7 +27,17 @@ any other batch size, such as the ragged last batch of a chunk, resolves
 staging to "t" for that workspace allocation (engine.hip_step._HipStep._alloc),
 so every batch size trains under either setting.
 
-Defaults come from env (SC_AMD_BK / SC_AMD_PRIO / SC_AMD_STAGING) and can be
+The TopK and BatchTopK steps also take a `topk_chain` choice for everything
+behind the selection:
+
+  topk_chain="dense"   dec_fwd, gc and two grad_w GEMMs over the full [M, B, n]
+                       code matrix (default)
+  topk_chain="sparse"  k_sparse_dec_gc + k_sparse_grad_w, which visit only the
+                       hits c > 0; d <= 2048.  Opt-in: measured in
+                       profiles/README.md, the default is a later decision
+
+Defaults come from env (SC_AMD_BK / SC_AMD_PRIO / SC_AMD_STAGING /
+SC_AMD_TOPK_CHAIN) and can be
 overridden per-process via set_kernel_config() — scripts/ktune.py sweeps the
 combinations on a GPU box and the measured winner is baked into DEFAULTS.
 """
@@ -61,6 +71,9 @@ DEFAULTS = {
     # dec's 0.83; the 128x256 tile halves their column panels (fewer
     # barriers per FLOP) at 2 blocks/CU — sweep via SC_AMD_BN_ENC.
     "bn_enc": None,
+    # what follows the selection in the TopK / BatchTopK steps: the "dense"
+    # GEMM chain or the "sparse" kernels over the hits (module docstring)
+    "topk_chain": "dense",
 }
 
 _cfg = dict(DEFAULTS)
@@ -79,6 +92,9 @@ if os.environ.get("SC_AMD_BK_DEC"):
     _cfg["bk_dec"] = int(os.environ["SC_AMD_BK_DEC"])
 if os.environ.get("SC_AMD_BN_ENC"):
     _cfg["bn_enc"] = int(os.environ["SC_AMD_BN_ENC"])
+if os.environ.get("SC_AMD_TOPK_CHAIN"):
+    _cfg["topk_chain"] = os.environ["SC_AMD_TOPK_CHAIN"]
+    assert _cfg["topk_chain"] in ("dense", "sparse"), "SC_AMD_TOPK_CHAIN must be dense or sparse"
 
 
 def kernel_config() -> dict:
@@ -93,3 +109,4 @@ def set_kernel_config(**kwargs) -> None:
     assert _cfg["bk"] in (16, 32) and _cfg["staging"] in ("pre", "t")
     assert _cfg["bn"] in (128, 256)
     assert _cfg["bn_enc"] in (None, 128, 256)
+    assert _cfg["topk_chain"] in ("dense", "sparse")
