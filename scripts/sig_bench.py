@@ -69,6 +69,13 @@ def build(sig_name, d, n, M, device):
         sig = BatchTopKEncoder
         models = [BatchTopKEncoder.init(d, n, 32) for _ in range(M)]
         no_stacking = True  # the selection is data-dependent, as for topk
+    elif sig_name == "matryoshka":
+        from sparse_coding_amd.models.matryoshka import MatryoshkaBatchTopKEncoder
+
+        sig = MatryoshkaBatchTopKEncoder
+        ends = [n // 16, n // 8, n // 4, n // 2, n]
+        models = [sig.init(d, n, 32, ends) for _ in range(M)]
+        no_stacking = True  # as batch_topk
     elif sig_name == "lista":
         sig = FunctionalLISTADenoisingSAE
         models = [sig.init(d, n, 3, float(l1)) for l1 in l1s]
@@ -123,7 +130,7 @@ def main():
     device = "cuda:0"
 
     sig_names = ("tied", "untied", "masked_tied", "thresholding", "reverse",
-                 "centered", "whitened", "positive", "topk", "batch_topk", "lista",
+                 "centered", "whitened", "positive", "topk", "batch_topk", "matryoshka", "lista",
                  "residual", "semilinear")
     if args.only:
         sig_names = tuple(s for s in sig_names if s in args.only.split(","))

@@ -25,10 +25,12 @@ hand-written gfx950 HIP kernels (``sparse_coding_amd/ops/hip/sae_kernels.hip``):
   k_topk_select  : per-row radix top-k + scatter (TopK)
   k_btk_hist/k_btk_write : batch-level radix top-k over many workgroups +
                    scatter + inference-threshold state (BatchTopK)
+  k_msparse_dec_gc/k_msparse_grad_w : the sparse chain with G nested prefix
+                   losses (Matryoshka BatchTopK)
 
 Fused-step coverage: EVERY trainable signature in the zoo — tied, untied,
 masked tied/untied, thresholding, reverse, tied-centered, positive-tied,
-TopK, BatchTopK, LISTA, residual-denoising and semilinear.
+TopK, BatchTopK, Matryoshka BatchTopK, LISTA, residual-denoising and semilinear.
 
 Structure.  Every step class derives from ``_HipStep``, which owns what
 does not depend on the signature: the Adam hyper-parameters, the kernel
@@ -108,6 +110,8 @@ def maybe_make_step(ensemble, required: bool = False) -> Optional["_HipStep"]:
         FunctionalLISTADenoisingSAE,
         FunctionalResidualDenoisingSAE,
     )
+    from sparse_coding_amd.engine.hip_matryoshka import HipMatryoshkaStep
+    from sparse_coding_amd.models.matryoshka import MatryoshkaBatchTopKEncoder
     from sparse_coding_amd.models.positive import FunctionalPositiveTiedSAE
     from sparse_coding_amd.models.semilinear import SemiLinearSAE
     from sparse_coding_amd.models.topk import TopKEncoder
@@ -118,6 +122,7 @@ def maybe_make_step(ensemble, required: bool = False) -> Optional["_HipStep"]:
     make = {
         TopKEncoder: HipTopKStep,
         BatchTopKEncoder: HipBatchTopKStep,
+        MatryoshkaBatchTopKEncoder: HipMatryoshkaStep,
         sigs.FunctionalThresholdingSAE: HipThresholdStep,
         sigs.FunctionalReverseSAE: sae(tied=True, reverse=True),
         sigs.FunctionalTiedCenteredSAE: HipCenteredStep,
@@ -1176,7 +1181,7 @@ class HipTopKStep(_HipStep):
             self.g_bias_scratch = f(M, n)
 
     def _grads(self, x, B, on_grads):
-        ext, bk, prio, bk_gw = self.ext, self.bk, self.prio, self.bk_gw
+        ext, bk, prio = self.ext, self.bk, self.prio
         W = self.ens.params["dict"]
 
         self.loss_parts.zero_()
@@ -1184,7 +1189,11 @@ class HipTopKStep(_HipStep):
         ext.enc_fwd(x, W, self.dummy_bias, self.inv_norms,
                     self.scores, self.loss_parts, self.fired, 1, bk, prio)
         self._select()
+        self._behind_selection(x, W, B, on_grads)
 
+    def _behind_selection(self, x, W, B, on_grads):
+        """codes c -> r, loss parts and the announced gw."""
+        ext, bk, prio, bk_gw = self.ext, self.bk, self.prio, self.bk_gw
         if self.kc["topk_chain"] == "sparse":
             ext.sparse_dec_gc(self.c, W, self.inv_norms, x, self.r, self.gpre, self.loss_parts)
             ext.sparse_grad_w(self.c, self.gpre, self.r, x, self.gw, self.hits, self.hit_counts)
@@ -1267,3 +1276,4 @@ class HipBatchTopKStep(HipTopKStep):
     def _loss_data(self, B: int):
         mse = self.loss_parts[:, 0] / (B * self.d_act)
         return {"loss": mse, "threshold": self.thr_batch}
+

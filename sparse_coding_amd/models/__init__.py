@@ -9,3 +9,6 @@ from sparse_coding_amd.models.sae_signatures import (
 )
 from sparse_coding_amd.models.topk import TopKEncoder, TopKLearnedDict
 from sparse_coding_amd.models.batch_topk import BatchTopKEncoder, BatchTopKLearnedDict
+from sparse_coding_amd.models.matryoshka import (
+    MatryoshkaBatchTopKEncoder, MatryoshkaBatchTopKLearnedDict,
+)

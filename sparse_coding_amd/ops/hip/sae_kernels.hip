@@ -77,7 +77,9 @@
 //   batch-level radix top-k over many workgroups), k_resample (K14 on-device),
 //   k_lista_bwd_elem (one-pass LISTA backward elementwise chain),
 //   k_sparse_dec_gc / k_sparse_grad_w (the TopK family's chain behind the
-//   selection over the hits c > 0 alone; no GEMM, see the end of this file)
+//   selection over the hits c > 0 alone; no GEMM, see the end of this file),
+//   k_msparse_dec_gc / k_msparse_grad_w (that chain with G nested prefix
+//   losses: Matryoshka BatchTopK)
 
 #include <hip/hip_runtime.h>
 
@@ -2223,3 +2225,260 @@ void k_sparse_grad_w(const float* __restrict__ c,     // [M, B, n]
     }
   }
 }
+
+// ---------------------------------------------------------------------------
+// Matryoshka BatchTopK (models/matryoshka.py): the features are cut into G <= 8
+// levels by the ascending ends e_0 < ... < e_{G-1} = n (`ends`, int32 [M, G]),
+// and the loss is the sum over g of mse(x, c[:, :e_g] @ What[:e_g]).  With
+// r_g = c[:, :e_g] @ What[:e_g] - x the residual of prefix g and
+// S_g = r_g + ... + r_{G-1}, a feature j of level g(j) has
+//   gpre[b,j] = (gscale inv[j]) dot(S_g(j)[b,:], W[j,:])
+//   gw[j,:]   = sum over its hit rows b of gscale c[b,j] S_g(j)[b,:] + gpre[b,j] x[b,:]
+// which is the plain chain with S_g(j) where that has r.  No level costs a GEMM:
+//
+//   k_msparse_dec_gc  k_sparse_dec_gc's wave per row.  Pass 0 scans the row
+//     level by level into the SAME accumulators (a level's scan is sdg_scan on
+//     the segment [e_{g-1}, e_g), its base pointers offset; a segment whose base
+//     is not 16-byte aligned takes the 64-wide ballot path).  The row is walked
+//     in ascending order and the accumulator is never reset, so at the boundary
+//     e_g it IS prefix g's reconstruction: r_g = acc - x goes to R[m, g, b, :]
+//     and its squares, summed as k_sparse_dec_gc sums them, to mse_parts[m, g]
+//     (one atomicAdd per level and block).  The last level's sum is the plain
+//     kernel's, bit for bit.  Pass 1 goes down from g = G-1 with S in the same
+//     registers (acc is dead): S = r_{G-1} as it stands, then S += r_g read back
+//     from R (the lane that wrote it reads it); S is stored over R[m, g, b, :]
+//     and segment g is rescanned for gpre at its hits.  A segment without a hit
+//     still gets its r_g and S.
+//   k_msparse_grad_w  k_sparse_grad_w's strip of 64 features, a feature's hits
+//     reading their residual rows from R[m, g(j)], which now holds S.  g(j)
+//     counts the ends <= j, wave-uniform; a strip may straddle a boundary.
+//
+// R costs 3 G B d floats of traffic per model (r_g out, back in, S out; the
+// last level is not rewritten).  Ends outside 0..n or out of order are clamped
+// into an ascending sequence: a bad `ends` gives wrong levels, never a wild
+// address.  The last level always ends at n.
+//
+// Registers and scratch, from the gfx950 code object's metadata as above.  The
+// level loop and the boundary epilogue cost k_msparse_dec_gc a few registers
+// over k_sparse_dec_gc; at DL = 16 that is more than 8 waves per SIMD leave
+// (64: the compiler spilled 32 bytes), so that depth asks for 4.  The waves
+// per SIMD below are what the launch bounds ask for and the VGPR counts allow
+// (512 / VGPRs): derived from the metadata, not observed on a device.
+//
+//   DL                       1    2    4    8   12   16   32
+//   k_msparse_dec_gc  VGPRs  26   24   27   38   52   71  182   (8 waves/SIMD asked for; 4 at DL = 16, 2 at DL = 32)
+//   k_msparse_grad_w  VGPRs  26   30   42   70  100  128  245   (4 waves/SIMD asked for; 2 at DL = 32)
+//   scratch bytes (both)     0    0    0    0    0    0    0
+// ---------------------------------------------------------------------------
+#define MSP_MAX_G 8
+
+// end of level g, clamped into [lo, n]; the last level ends at n
+SPK_DEV int msp_end(const int* __restrict__ ends_m, int g, int G, int lo, int n) {
+  if (g == G - 1) return n;
+  const int e = ends_m[g];
+  return e < lo ? lo : spk_min(e, n);
+}
+
+template <int DL, int MINW>
+__global__ __launch_bounds__(SDG_T, MINW) SPK_NOPK
+void k_msparse_dec_gc(const float* __restrict__ c,          // [M, B, n]
+                      const float* __restrict__ Wdec,       // [M, n, d]
+                      const float* __restrict__ inv_norms,  // [M, n]
+                      const float* __restrict__ x,          // [B, d] or [M, B, d]
+                      const int* __restrict__ ends,         // [M, G]
+                      float* R,                             // [M, G, B, d]: r_g, then S_g
+                      float* __restrict__ gpre,             // [M, B, n], written at the hits only
+                      float* __restrict__ mse_parts,        // [M, G]
+                      int B, int d, int n, int G, long x_mstride) {
+  __shared__ float wave_ss[MSP_MAX_G][SDG_T / WAVE];
+  const int lane = spk_tid() & (WAVE - 1);
+  const int wave = spk_wave_id();
+  const int m = (int)__builtin_amdgcn_workgroup_id_y();
+  const int b = (int)__builtin_amdgcn_workgroup_id_x() * (SDG_T / WAVE) + wave;
+  const int* ends_m = ends + (long)m * G;
+
+  if (b < B) {
+    const float* crow = c + ((long)m * B + b) * n;
+    const float* W = Wdec + (long)m * n * d;
+    const float* inv = inv_norms + (long)m * n;
+    const float* xrow = x + (long)m * x_mstride + (long)b * d;
+    float* Rrow = R + ((long)m * G * B + b) * d;  // level g's row: + g * level
+    const long level = (long)B * d;
+    float* grow = gpre + ((long)m * B + b) * n;
+    const float gscale = 2.0f / ((float)B * (float)d);
+
+    float acc[DL];
+#pragma unroll
+    for (int i = 0; i < DL; ++i) acc[i] = 0.f;
+    int e0 = 0;
+    for (int g = 0; g < G; ++g) {
+      const int e1 = msp_end(ends_m, g, G, e0, n);
+      sdg_scan<DL, 0>(acc, crow + e0, e1 - e0, W + (long)e0 * d, inv + e0, grow + e0, gscale, d, lane);
+      float* rrow = Rrow + g * level;
+      const bool last = g == G - 1;
+      float ss = 0.f;
+#pragma unroll
+      for (int i = 0; i < DL; ++i) {
+        const int col = lane + i * WAVE;
+        float rv = 0.f;  // columns past d stay 0 for the dots of pass 1
+        if (col < d) {
+          rv = acc[i] - xrow[col];
+          rrow[col] = rv;
+        }
+        if (last) acc[i] = rv;  // S_{G-1} = r_{G-1}
+        ss = __builtin_fmaf(rv, rv, ss);
+      }
+      ss = spk_wave_sum(ss, lane);
+      if (lane == 0) wave_ss[g][wave] = ss;
+      e0 = e1;
+    }
+    for (int g = G - 1; g >= 0; --g) {
+      // the clamped ends again, from the top: e1 of level g is e0 of level g + 1
+      int lo = 0;
+      for (int h = 0; h < g; ++h) lo = msp_end(ends_m, h, G, lo, n);
+      const int e1 = msp_end(ends_m, g, G, lo, n);
+      if (g < G - 1) {
+        float* rrow = Rrow + g * level;
+#pragma unroll
+        for (int i = 0; i < DL; ++i) {
+          const int col = lane + i * WAVE;
+          if (col < d) {
+            acc[i] += rrow[col];
+            rrow[col] = acc[i];
+          }
+        }
+      }
+      sdg_scan<DL, 1>(acc, crow + lo, e1 - lo, W + (long)lo * d, inv + lo, grow + lo, gscale, d, lane);
+    }
+  } else {
+    for (int g = lane; g < G; g += WAVE) wave_ss[g][wave] = 0.f;
+  }
+  spk_barrier();
+  if (spk_tid() < G) {
+    const float* ws = wave_ss[spk_tid()];
+    __hip_atomic_fetch_add(&mse_parts[m * G + spk_tid()], (ws[0] + ws[1]) + (ws[2] + ws[3]),
+                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// R[m, g(j)]: the [B, d] block feature j's hits read their residual rows from
+SPK_DEV const float* msp_level_rows(const float* __restrict__ R_m, const int* __restrict__ ends_m,
+                                    int j, int G, int n, long level) {
+  int g = 0, lo = 0;
+  for (int h = 0; h < G - 1; ++h) {
+    lo = msp_end(ends_m, h, G, lo, n);
+    g += lo <= j ? 1 : 0;
+  }
+  return R_m + g * level;
+}
+
+// k_sparse_grad_w's phases, statement for statement (that kernel's code object
+// is pinned, so the body is repeated here and not shared): the two
+// sgw_accum calls take a feature's own level of R.
+template <int DL, int MINW>
+__global__ __launch_bounds__(SGW_T, MINW) SPK_NOPK
+void k_msparse_grad_w(const float* __restrict__ c,     // [M, B, n]
+                      const float* __restrict__ gpre,  // [M, B, n], read at the hits only
+                      const float* __restrict__ R,     // [M, G, B, d]: S_g
+                      const float* __restrict__ x,     // [B, d] or [M, B, d]
+                      const int* __restrict__ ends,    // [M, G]
+                      float* __restrict__ gw,          // [M, n, d]
+                      int* hits,                       // [M, n, B] ascending hit rows per feature
+                      int* __restrict__ hit_counts,    // [M, n]
+                      int B, int d, int n, int G, long x_mstride) {
+  constexpr int CW = DL * WAVE < SGW_CW_MAX ? DL * WAVE : SGW_CW_MAX;
+  constexpr int NH = DL * WAVE / CW;  // combine rounds
+  constexpr int RPH = CW / WAVE;      // registers per round
+  __shared__ int cnt[SGW_NW][SGW_STRIP];
+  __shared__ int tot[SGW_STRIP];
+  __shared__ float part[SGW_NW][CW];
+
+  const int lane = spk_tid() & (WAVE - 1);
+  const int wave = spk_wave_id();
+  const int m = (int)__builtin_amdgcn_workgroup_id_y();
+  const int j0 = (int)__builtin_amdgcn_workgroup_id_x() * SGW_STRIP;
+  const long level = (long)B * d;
+  const float* c_m = c + (long)m * B * n;
+  const float* g_m = gpre + (long)m * B * n;
+  const float* R_m = R + (long)m * G * level;
+  const int* ends_m = ends + (long)m * G;
+  const float* x_m = x + (long)m * x_mstride;
+  float* gw_m = gw + (long)m * n * d;
+  const float gscale = 2.0f / ((float)B * (float)d);
+
+  // ---- phase 1: thread (slice = wave, feature = lane) ----------------------
+  {
+    const int j = j0 + lane;
+    const bool j_ok = j < n;
+    const int per = (B + SGW_NW - 1) / SGW_NW;
+    const int b_lo = spk_min(B, wave * per), b_hi = spk_min(B, b_lo + per);
+    const float* ccol = c_m + (j_ok ? j : 0);
+    int k = 0;
+    if (j_ok) {
+#pragma unroll 8
+      for (int b = b_lo; b < b_hi; ++b) k += ccol[(long)b * n] > 0.f ? 1 : 0;
+    }
+    cnt[wave][lane] = k;
+    spk_barrier();
+    int off = 0, total = 0;
+#pragma unroll
+    for (int s = 0; s < SGW_NW; ++s) {
+      const int v = cnt[s][lane];
+      if (s < wave) off += v;
+      total += v;
+    }
+    if (j_ok) {
+      int* list = hits + ((long)m * n + j) * B;
+#pragma unroll 8
+      for (int b = b_lo; b < b_hi; ++b)
+        if (ccol[(long)b * n] > 0.f) list[off++] = b;
+    }
+    if (wave == 0) {
+      tot[lane] = j_ok ? total : 0;
+      if (j_ok) hit_counts[(long)m * n + j] = total;
+    }
+    spk_fence_device();
+    spk_barrier();
+    spk_fence_device();
+  }
+
+  // ---- phase 2a: light features, one wave each ------------------------------
+  float acc[DL];
+  for (int f = wave; f < SGW_STRIP && j0 + f < n; f += SGW_NW) {
+    const int j = j0 + f;
+    const int count = tot[f];
+    if (count > SGW_LIGHT) continue;
+    sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, 0, count, c_m + j, g_m + j,
+                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, d, lane);
+#pragma unroll
+    for (int i = 0; i < DL; ++i) {
+      const int col = lane + i * WAVE;
+      if (col < d) gw_m[(long)j * d + col] = acc[i];
+    }
+  }
+
+  // ---- phase 2b: heavy features, all waves each -----------------------------
+  for (int f = 0; f < SGW_STRIP && j0 + f < n; ++f) {
+    const int count = tot[f];
+    if (count <= SGW_LIGHT) continue;  // block-uniform
+    const int j = j0 + f;
+    const int per = (count + SGW_NW - 1) / SGW_NW;
+    const int lo = spk_min(count, wave * per), hi = spk_min(count, lo + per);
+    sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, lo, hi, c_m + j, g_m + j,
+                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, d, lane);
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+#pragma unroll
+      for (int ii = 0; ii < RPH; ++ii) part[wave][ii * WAVE + lane] = acc[h * RPH + ii];
+      spk_barrier();
+      for (int col = spk_tid(); col < CW && h * CW + col < d; col += SGW_T) {
+        float s = part[0][col];
+#pragma unroll
+        for (int w = 1; w < SGW_NW; ++w) s += part[w][col];
+        gw_m[(long)j * d + h * CW + col] = s;
+      }
+      spk_barrier();
+    }
+  }
+}
+

@@ -515,6 +515,71 @@ void sparse_grad_w(torch::Tensor c, torch::Tensor gpre, torch::Tensor r, torch::
 #undef LAUNCH_SGW
 }
 
+// The Matryoshka chain (k_msparse_dec_gc / k_msparse_grad_w): the sparse chain
+// with G nested levels.  ends is int32 [M, G], R is [M, G, B, d] (r_g out of
+// the decode's first pass, S_g = r_g + ... + r_{G-1} when it returns) and
+// mse_parts [M, G] is accumulated into, as loss_parts is.
+static int msparse_levels(const char* who, const SparseShape& s, const torch::Tensor& ends,
+                          const torch::Tensor& R) {
+  TORCH_CHECK(ends.dim() == 2 && ends.size(0) == s.M, who, ": ends must be int32 [M,G]");
+  const long G = ends.size(1);
+  TORCH_CHECK(G >= 1 && G <= MSP_MAX_G, who, ": G = ", G, " is outside 1..", MSP_MAX_G);
+  TORCH_CHECK(R.dim() == 4 && R.size(0) == s.M && R.size(1) == G && R.size(2) == s.B && R.size(3) == s.d,
+              who, ": R must be [M,G,B,d]");
+  return (int)G;
+}
+
+void msparse_dec_gc(torch::Tensor c, torch::Tensor W, torch::Tensor inv_norms, torch::Tensor x,
+                    torch::Tensor ends, torch::Tensor R, torch::Tensor gpre, torch::Tensor mse_parts) {
+  CHECK_IN(c); CHECK_IN(W); CHECK_IN(inv_norms); CHECK_IN(x); CHECK_IN(R); CHECK_IN(gpre);
+  CHECK_IN(mse_parts);
+  TORCH_CHECK(R.dim() == 4, "msparse_dec_gc: R must be [M,G,B,d]");
+  const SparseShape s = sparse_shape("msparse_dec_gc", c, gpre, R.select(1, 0), x);
+  const int G = msparse_levels("msparse_dec_gc", s, ends, R);
+  TORCH_CHECK(W.dim() == 3 && W.size(0) == s.M && W.size(1) == s.n && W.size(2) == s.d,
+              "msparse_dec_gc: W must be [M,n,d]");
+  TORCH_CHECK(inv_norms.numel() == (long)s.M * s.n, "msparse_dec_gc: inv_norms must be [M,n]");
+  TORCH_CHECK(mse_parts.dim() == 2 && mse_parts.size(0) == s.M && mse_parts.size(1) == G,
+              "msparse_dec_gc: mse_parts must be [M,G]");
+  const int* ends_p = int32_ptr(ends, "ends");
+  if (s.M == 0 || s.B == 0) return;
+  dim3 grid(cdiv(s.B, SDG_T / WAVE), s.M);
+#define LAUNCH_MSDG(DL)                                                                       \
+  hipLaunchKernelGGL((k_msparse_dec_gc<DL, (DL <= 12 ? 8 : DL <= 16 ? 4 : 2)>), grid,         \
+                     dim3(SDG_T), 0,                                                          \
+                     cur_stream(), c.data_ptr<float>(), W.data_ptr<float>(),                  \
+                     inv_norms.data_ptr<float>(), x.data_ptr<float>(), ends_p,                \
+                     R.data_ptr<float>(), gpre.data_ptr<float>(), mse_parts.data_ptr<float>(), \
+                     s.B, s.d, s.n, G, s.x_mstride)
+  SPARSE_DISPATCH_DL(s.d, LAUNCH_MSDG);
+#undef LAUNCH_MSDG
+}
+
+void msparse_grad_w(torch::Tensor c, torch::Tensor gpre, torch::Tensor R, torch::Tensor x,
+                    torch::Tensor ends, torch::Tensor gw, torch::Tensor hits, torch::Tensor hit_counts) {
+  CHECK_IN(c); CHECK_IN(gpre); CHECK_IN(R); CHECK_IN(x); CHECK_IN(gw);
+  TORCH_CHECK(R.dim() == 4, "msparse_grad_w: R must be [M,G,B,d]");
+  const SparseShape s = sparse_shape("msparse_grad_w", c, gpre, R.select(1, 0), x);
+  const int G = msparse_levels("msparse_grad_w", s, ends, R);
+  TORCH_CHECK(gw.dim() == 3 && gw.size(0) == s.M && gw.size(1) == s.n && gw.size(2) == s.d,
+              "msparse_grad_w: gw must be [M,n,d]");
+  TORCH_CHECK(hits.numel() >= sparse_hits_size(s.M, s.B, s.n),
+              "msparse_grad_w: hits needs sparse_hits_size(M, B, n) int32 elements");
+  TORCH_CHECK(hit_counts.numel() == (long)s.M * s.n, "msparse_grad_w: hit_counts must be [M,n]");
+  const int* ends_p = int32_ptr(ends, "ends");
+  int* hits_p = int32_ptr(hits, "hits");
+  int* counts_p = int32_ptr(hit_counts, "hit_counts");
+  if (s.M == 0 || s.n == 0) return;
+  dim3 grid(cdiv(s.n, SGW_STRIP), s.M);
+#define LAUNCH_MSGW(DL)                                                                       \
+  hipLaunchKernelGGL((k_msparse_grad_w<DL, (DL <= 16 ? 4 : 2)>), grid, dim3(SGW_T), 0,        \
+                     cur_stream(), c.data_ptr<float>(), gpre.data_ptr<float>(),               \
+                     R.data_ptr<float>(), x.data_ptr<float>(), ends_p, gw.data_ptr<float>(),  \
+                     hits_p, counts_p, s.B, s.d, s.n, G, s.x_mstride)
+  SPARSE_DISPATCH_DL(s.d, LAUNCH_MSGW);
+#undef LAUNCH_MSGW
+}
+
 void resample(torch::Tensor fired, torch::Tensor new_rows, torch::Tensor enc_scale,
               torch::Tensor W, torch::Tensor mu_w, torch::Tensor nu_w,
               c10::optional<torch::Tensor> dec,
@@ -610,6 +675,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("sparse_grad_w", &sparse_grad_w,
         "gw[j,:] = sum over the hit rows of gscale c r + gpre x; no atomics, every row written",
         py::arg("c"), py::arg("gpre"), py::arg("r"), py::arg("x"), py::arg("gw"),
+        py::arg("hits"), py::arg("hit_counts"));
+  m.def("msparse_dec_gc", &msparse_dec_gc,
+        "Matryoshka chain over the hits c > 0: the G prefix residuals into R, left as their suffix "
+        "sums S_g (+MSE partial per level), gpre at the hits only",
+        py::arg("c"), py::arg("W"), py::arg("inv_norms"), py::arg("x"), py::arg("ends"), py::arg("R"),
+        py::arg("gpre"), py::arg("mse_parts"));
+  m.def("msparse_grad_w", &msparse_grad_w,
+        "sparse_grad_w with a feature's residual rows read from its level of R",
+        py::arg("c"), py::arg("gpre"), py::arg("R"), py::arg("x"), py::arg("ends"), py::arg("gw"),
         py::arg("hits"), py::arg("hit_counts"));
   m.def("resample", &resample, "fused dead-neuron resample (K14): rank dead, rewrite rows, zero Adam state",
         py::arg("fired"), py::arg("new_rows"), py::arg("enc_scale"),

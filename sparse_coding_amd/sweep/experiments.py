@@ -23,6 +23,7 @@ import torch
 from sparse_coding_amd.engine.ensemble import FunctionalEnsemble
 from sparse_coding_amd.functional.optim import adam
 from sparse_coding_amd.models.batch_topk import BatchTopKEncoder
+from sparse_coding_amd.models.matryoshka import MatryoshkaBatchTopKEncoder
 from sparse_coding_amd.models.sae_signatures import (
     FunctionalMaskedTiedSAE,
     FunctionalSAE,
@@ -164,6 +165,25 @@ def batch_topk_init(cfg, ks: Sequence[int] = (4, 8, 16, 32, 64, 128)):
     )
 
 
+def matryoshka_init(cfg, ks: Sequence[int] = (4, 8, 16, 32, 64, 128), n_levels: int = 5):
+    """Matryoshka BatchTopK encoders across sparsity levels: batch_topk_init
+    with the nested-prefix loss, the levels ending at n/2^(G-1), ..., n/2, n."""
+    d = cfg.activation_width
+    devices = default_devices()
+    n_dict = int(d * cfg.learned_dict_ratio)
+    ends = [n_dict >> s for s in range(n_levels - 1, -1, -1)]
+    models = [MatryoshkaBatchTopKEncoder.init(d, n_dict, int(k), ends) for k in ks]
+    ens = FunctionalEnsemble(models, MatryoshkaBatchTopKEncoder, adam, {"lr": cfg.lr}, device=devices[0],
+                             no_stacking=True)
+    args = {"batch_size": cfg.batch_size, "device": devices[0], "dict_size": n_dict}
+    return (
+        [(ens, args, "matryoshka")],
+        ["dict_size"],
+        ["sparsity"],
+        {"sparsity": list(ks), "dict_size": [n_dict]},
+    )
+
+
 def thresholding_init(cfg):
     """Soft-thresholding SAEs (reference :403-494)."""
     return make_grid_ensembles(cfg, FunctionalThresholdingSAE, np.logspace(-4, -2, 8))
@@ -187,6 +207,10 @@ def run_topk(cfg):
 
 def run_batch_topk(cfg):
     return sweep(batch_topk_init, cfg)
+
+
+def run_matryoshka(cfg):
+    return sweep(matryoshka_init, cfg)
 
 
 def run_across_layers(cfg, layers: Sequence[int], init: Callable = dense_l1_range_init):
