@@ -303,10 +303,13 @@ def case(name) -> Case:
 # of a shallow chain.  The deep chains flip masks too easily there (LISTA has
 # 4-8 near-knee arguments per seed), so they get RAGGED_DEEP: a row tail, two
 # column tiles, a K tail of 4 at depth 16, K = 20 < 32, K = 132 for dec_fwd and
-# K = 36 for grad_w.  PRE runs the pre-transposed pipeline.
+# K = 36 for grad_w.  PRE runs the pre-transposed pipeline.  DEEP_D is not in
+# GRID: the sparse and Matryoshka step tests run it for a register depth
+# (16, entered from below: ceil(772 / 64) = 13) between those of the shapes above.
 ALIGNED = (2, 128, 64, 128)
 RAGGED = (2, 130, 68, 260)
 RAGGED_DEEP = (2, 36, 20, 132)
+DEEP_D = (2, 36, 772, 132)
 PRE = (2, 132, 68, 132)
 DEEP = ("lista", "residual", "semilinear")
 
