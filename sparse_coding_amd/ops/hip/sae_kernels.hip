@@ -668,7 +668,10 @@ void k_enc_fwd_t(const float* x,                    // [B, d]     (staged operan
     } else if (mode == ENC_REVERSE) {
       // reverse SAE (sae_ensemble.py:447-503): code = pre * [pre + b > 0]
       // (the bias is removed from active features before decoding, so the
-      // code can be negative and the L1 partial needs |code|)
+      // code can be negative and the L1 partial needs |code|).  fired counts
+      // code > 0 as in every other mode and as EnsembleResampler.observe
+      // does from aux["c"]: an active feature with a negative code has not
+      // fired.
       float bj = col_ok ? bias_m[col] : 0.f;
       float fired_cnt = 0.f;
       rows([&](int r, auto at) {
@@ -676,7 +679,7 @@ void k_enc_fwd_t(const float* x,                    // [B, d]     (staged operan
         float v = (pre + bj > 0.f) ? pre : 0.f;
         at(c_m) = v;
         l1_sum += fabsf(v);
-        fired_cnt += (v != 0.f) ? 1.f : 0.f;
+        fired_cnt += (v > 0.f) ? 1.f : 0.f;
       });
       add_fired(fired_cnt);
     } else {  // ENC_RELU

@@ -277,7 +277,14 @@ def enc_reverse(x, W, bias):
     """mode 3, the reverse SAE's code pre * [pre + b > 0], taken from
     FunctionalReverseSAE.loss in fp64.  The value carries c_dot(d)+c_scale(d)
     roundings, the decision variable one more (the bias add).  The mask is a
-    jump, so undecided elements are skipped for the code as well."""
+    jump, so undecided elements are skipped for the code as well.
+
+    A feature fires where its code is positive, the rule of every other
+    epilogue and of EnsembleResampler.observe on the torch backend; an active
+    feature with a negative code does not.  `on` holds the elements that fire
+    whatever the roundings do, `fired_undecided` those that may or may not: an
+    undecided mask whose pre can come out positive, or a decided one whose pre
+    lies within its own error of zero."""
     pre, absdot, c = enc_pre(x, W, True)
     M = pre.shape[0]
     codes = []
@@ -291,7 +298,8 @@ def enc_reverse(x, W, bias):
     b = d64(bias)[:, None, :]
     und = (pre + b).abs() <= (c + 1) * U * (absdot + b.abs())
     e = c * U * absdot
-    return {"c": code, "e": e, "undecided": und, "on": (code != 0) & ~und,
+    fired_und = (und & (pre > -e)) | (~und & (code != 0) & (code.abs() <= e))
+    return {"c": code, "e": e, "undecided": und, "on": (code > e) & ~und, "fired_undecided": fired_und,
             "flip": torch.where(und, pre.abs() + e, torch.zeros_like(e))}
 
 

@@ -25,6 +25,10 @@ knowledge of a step's internals.
   inputs where no decision is within rounding of its knee; ``SEEDS`` holds, per
   grid entry, the first seed for which that is so, found on the CPU from the
   reference alone.
+* ``SEQ_GRID`` / ``seq_models`` / ``seq_reference``: one pair of models per
+  case and six batches of three sizes against them, each batch with its own
+  first clean seed (``SEQ_SEEDS``) and its own reference: what
+  test_hip_step_sequence_gpu.py drives a step through, batch size changing.
 * ``compare`` / ``compare_losses``: the comparators.
 * ``doctored``: fp32 autograd gradients of deliberately wrong problems, which
   the comparator has to reject.
@@ -527,8 +531,12 @@ def decisions(name, shape, seed=None):
     """{"near": total count of near-knee arguments of the float64 forward over
     both models, "margin": the smallest nonzero relative distance from a knee,
     "records": one entry per decision op and model}."""
-    c = case(name)
     models, x = build(name, shape, seed)
+    return _decisions(name, models, x)
+
+
+def _decisions(name, models, x):
+    c = case(name)
     records, x64 = [], x.double()
     for m, (p, b) in enumerate(models):
         p, b = _cast(p, torch.float64), _cast(b, torch.float64)
@@ -540,11 +548,172 @@ def decisions(name, shape, seed=None):
             "records": records}
 
 
-def first_clean_seed(name, shape, limit=64):
+def first_clean_seed(name, shape, limit=None, batch=None):
+    """The first seed at which decisions() is clean: of a grid entry's models
+    and batch together (limit 64); or, with shape = (d, n) and batch = (B,
+    index), of that sequence batch against the sequence's fixed models (limit
+    256: the search runs per batch, so it adds over a sequence)."""
+    limit = limit or (64 if batch is None else 256)
     for seed in range(limit):
-        if decisions(name, tuple(shape), seed)["near"] == 0:
+        dec = decisions(name, tuple(shape), seed) if batch is None else seq_decisions(name, tuple(shape), *batch, seed)
+        if dec["near"] == 0:
             return seed
-    raise RuntimeError(f"{name} {shape}: no clean seed below {limit}")
+    raise RuntimeError(f"{name} {shape} {batch or ''}: no clean seed below {limit}")
+
+
+# ---------------------------------------------------------------------------
+# sequences: one pair of models, batches of changing size
+# ---------------------------------------------------------------------------
+
+# A training chunk ends on a short batch and the next one starts at the full
+# size again, so a fused step reallocates its workspaces, resolves its kernel
+# configuration and captures its graph again in mid-run.  A sequence is the two
+# models of build(name, (2, B_a, d, n)) and six batches against them: three at
+# B_a, one at B_b, two at B_c.
+#   132: a multiple of 4 (staging="pre" holds), ragged against the 128-row tile;
+#   37:  odd ("pre" must resolve to "t" and later back), one partial row tile;
+#   260: grows every workspace past what was allocated before;
+#   128, 256: the guard-free kernels, with 37 between them forcing the guarded.
+# variant: None, "pre" (staging), "sparse" (topk_chain), or "matryoshka" (the
+# batch_topk models with SEQ_GROUP_ENDS under the Matryoshka signature, as
+# test_matryoshka_gpu reuses batch_topk's grid entries).
+SEQ_SHALLOW = ((68, 260), (132, 37, 260))
+SEQ_DEEP = ((20, 132), (36, 17, 40))
+SEQ_ALIGNED = ((64, 128), (128, 37, 256))
+SEQ_PRE = ((68, 132), (132, 37, 136))
+SEQ_GROUP_ENDS = ((64, 128, 260), (37, 101, 260))
+
+
+def _seq_grid():
+    g = [(c.name,) + (SEQ_DEEP if c.name in DEEP else SEQ_SHALLOW) + (None,) for c in cases()]
+    g += [(name,) + SEQ_ALIGNED + (None,) for name in ("tied", "topk", "batch_topk")]
+    g += [(name,) + SEQ_PRE + ("pre",) for name in ("tied", "untied", "masked_tied")]
+    g += [("topk",) + SEQ_SHALLOW + ("sparse",), ("batch_topk",) + SEQ_SHALLOW + ("sparse",),
+          ("batch_topk",) + SEQ_SHALLOW + ("matryoshka",)]
+    return g
+
+
+SEQ_GRID = _seq_grid()
+# batch -> (which of B_a, B_b, B_c, index among the batches of that size)
+SEQ_BATCHES = {"a1": (0, 0), "a2": (0, 1), "a3": (0, 2), "b1": (1, 0), "c1": (2, 0), "c2": (2, 1)}
+# the twelve calls and what GraphReplay has to make of each; a class that does
+# not capture runs all of them eagerly
+SEQ_CALLS = (("a1", "eager"), ("a2", "eager"), ("a3", "captured"), ("a1", "replayed"),
+             ("b1", "eager"), ("c1", "eager"), ("c2", "eager"), ("c1", "captured"),
+             ("a2", "eager"), ("a3", "eager"), ("a1", "captured"), ("a2", "replayed"))
+# one (B_a, B_b, B_c) per (case, (d, n)): SEQ_SEEDS' key need not name B_a
+SEQ_BS = {(name, dn): Bs for name, dn, Bs, _ in SEQ_GRID}
+assert all(SEQ_BS[(name, dn)] == Bs for name, dn, Bs, _ in SEQ_GRID)
+
+
+def seq_id(entry):
+    name, dn, Bs, variant = entry
+    return f"{name}-{'x'.join(map(str, dn))}-{'-'.join(map(str, Bs))}" + (f"-{variant}" if variant else "")
+
+
+# SEQ_SEEDS[(case, (d, n), B, index)]: per batch the first seed of 0, 1, 2, ...
+# at which decisions() of (the sequence's models, that batch) reports no
+# near-knee argument (test_step_reference_cpu.test_seq_seeds_are_the_first_clean_ones).
+# Every batch has a clean seed below 256 at the size the table above names: no
+# batch had to shrink.
+SEQ_SEEDS: dict = {
+    ('tied', (68, 260), 132, 0): 1, ('tied', (68, 260), 132, 1): 3, ('tied', (68, 260), 132, 2): 1,
+    ('tied', (68, 260), 37, 0): 3, ('tied', (68, 260), 260, 0): 0, ('tied', (68, 260), 260, 1): 3,
+    ('untied', (68, 260), 132, 0): 2, ('untied', (68, 260), 132, 1): 6, ('untied', (68, 260), 132, 2): 1,
+    ('untied', (68, 260), 37, 0): 0, ('untied', (68, 260), 260, 0): 5, ('untied', (68, 260), 260, 1): 5,
+    ('masked_tied', (68, 260), 132, 0): 1, ('masked_tied', (68, 260), 132, 1): 3,
+    ('masked_tied', (68, 260), 132, 2): 1, ('masked_tied', (68, 260), 37, 0): 3,
+    ('masked_tied', (68, 260), 260, 0): 0, ('masked_tied', (68, 260), 260, 1): 3,
+    ('masked_untied', (68, 260), 132, 0): 2, ('masked_untied', (68, 260), 132, 1): 6,
+    ('masked_untied', (68, 260), 132, 2): 1, ('masked_untied', (68, 260), 37, 0): 0,
+    ('masked_untied', (68, 260), 260, 0): 5, ('masked_untied', (68, 260), 260, 1): 5,
+    ('reverse', (68, 260), 132, 0): 3, ('reverse', (68, 260), 132, 1): 1, ('reverse', (68, 260), 132, 2): 2,
+    ('reverse', (68, 260), 37, 0): 0, ('reverse', (68, 260), 260, 0): 2, ('reverse', (68, 260), 260, 1): 18,
+    ('centered', (68, 260), 132, 0): 0, ('centered', (68, 260), 132, 1): 1, ('centered', (68, 260), 132, 2): 5,
+    ('centered', (68, 260), 37, 0): 0, ('centered', (68, 260), 260, 0): 12, ('centered', (68, 260), 260, 1): 0,
+    ('whitened', (68, 260), 132, 0): 6, ('whitened', (68, 260), 132, 1): 0, ('whitened', (68, 260), 132, 2): 0,
+    ('whitened', (68, 260), 37, 0): 1, ('whitened', (68, 260), 260, 0): 13, ('whitened', (68, 260), 260, 1): 0,
+    ('positive', (68, 260), 132, 0): 2, ('positive', (68, 260), 132, 1): 3, ('positive', (68, 260), 132, 2): 3,
+    ('positive', (68, 260), 37, 0): 0, ('positive', (68, 260), 260, 0): 1, ('positive', (68, 260), 260, 1): 7,
+    ('thresholding', (68, 260), 132, 0): 11, ('thresholding', (68, 260), 132, 1): 1,
+    ('thresholding', (68, 260), 132, 2): 2, ('thresholding', (68, 260), 37, 0): 0,
+    ('thresholding', (68, 260), 260, 0): 1, ('thresholding', (68, 260), 260, 1): 6,
+    ('lista', (20, 132), 36, 0): 5, ('lista', (20, 132), 36, 1): 3, ('lista', (20, 132), 36, 2): 1,
+    ('lista', (20, 132), 17, 0): 2, ('lista', (20, 132), 40, 0): 6, ('lista', (20, 132), 40, 1): 0,
+    ('residual', (20, 132), 36, 0): 2, ('residual', (20, 132), 36, 1): 0, ('residual', (20, 132), 36, 2): 0,
+    ('residual', (20, 132), 17, 0): 0, ('residual', (20, 132), 40, 0): 0, ('residual', (20, 132), 40, 1): 3,
+    ('semilinear', (20, 132), 36, 0): 0, ('semilinear', (20, 132), 36, 1): 0, ('semilinear', (20, 132), 36, 2): 0,
+    ('semilinear', (20, 132), 17, 0): 0, ('semilinear', (20, 132), 40, 0): 0, ('semilinear', (20, 132), 40, 1): 1,
+    ('topk', (68, 260), 132, 0): 0, ('topk', (68, 260), 132, 1): 0, ('topk', (68, 260), 132, 2): 2,
+    ('topk', (68, 260), 37, 0): 0, ('topk', (68, 260), 260, 0): 0, ('topk', (68, 260), 260, 1): 0,
+    ('batch_topk', (68, 260), 132, 0): 4, ('batch_topk', (68, 260), 132, 1): 2,
+    ('batch_topk', (68, 260), 132, 2): 1, ('batch_topk', (68, 260), 37, 0): 0,
+    ('batch_topk', (68, 260), 260, 0): 17, ('batch_topk', (68, 260), 260, 1): 5,
+    ('tied', (64, 128), 128, 0): 0, ('tied', (64, 128), 128, 1): 0, ('tied', (64, 128), 128, 2): 0,
+    ('tied', (64, 128), 37, 0): 0, ('tied', (64, 128), 256, 0): 0, ('tied', (64, 128), 256, 1): 0,
+    ('topk', (64, 128), 128, 0): 0, ('topk', (64, 128), 128, 1): 0, ('topk', (64, 128), 128, 2): 0,
+    ('topk', (64, 128), 37, 0): 0, ('topk', (64, 128), 256, 0): 0, ('topk', (64, 128), 256, 1): 0,
+    ('batch_topk', (64, 128), 128, 0): 1, ('batch_topk', (64, 128), 128, 1): 0,
+    ('batch_topk', (64, 128), 128, 2): 0, ('batch_topk', (64, 128), 37, 0): 0,
+    ('batch_topk', (64, 128), 256, 0): 3, ('batch_topk', (64, 128), 256, 1): 4,
+    ('tied', (68, 132), 132, 0): 1, ('tied', (68, 132), 132, 1): 1, ('tied', (68, 132), 132, 2): 0,
+    ('tied', (68, 132), 37, 0): 0, ('tied', (68, 132), 136, 0): 0, ('tied', (68, 132), 136, 1): 0,
+    ('untied', (68, 132), 132, 0): 0, ('untied', (68, 132), 132, 1): 0, ('untied', (68, 132), 132, 2): 1,
+    ('untied', (68, 132), 37, 0): 0, ('untied', (68, 132), 136, 0): 0, ('untied', (68, 132), 136, 1): 2,
+    ('masked_tied', (68, 132), 132, 0): 1, ('masked_tied', (68, 132), 132, 1): 1,
+    ('masked_tied', (68, 132), 132, 2): 0, ('masked_tied', (68, 132), 37, 0): 0,
+    ('masked_tied', (68, 132), 136, 0): 0, ('masked_tied', (68, 132), 136, 1): 0,
+}
+
+
+def seq_models(name, dn, variant=None):
+    """The sequence's two models: those of build(name, (2, B_a, d, n)), so that
+    a SEEDS entry for that shape is reused where there is one."""
+    models, _ = build(name, (2, SEQ_BS[(name, tuple(dn))][0]) + tuple(dn))
+    if variant == "matryoshka":
+        models = [(p, dict(b, group_ends=torch.tensor(e))) for (p, b), e in zip(models, SEQ_GROUP_ENDS)]
+    return models
+
+
+def seq_batch(name, dn, B, index, seed=None):
+    """Batch `index` of size B: its own generator, seeded apart from every other
+    (B, index) and from build()'s."""
+    seed = SEQ_SEEDS[(name, tuple(dn), B, index)] if seed is None else seed
+    assert 0 <= seed < 10_000 and 0 <= index < 100
+    gen = torch.Generator().manual_seed(1_000_000 * B + 10_000 * (index + 1) + seed)
+    return case(name).x_scale * _randn(gen, B, dn[0])
+
+
+@functools.lru_cache(maxsize=None)
+def seq_decisions(name, dn, B, index, seed=None):
+    """decisions() of the sequence's models on one of its batches."""
+    return _decisions(name, seq_models(name, dn), seq_batch(name, dn, B, index, seed))
+
+
+def seq_x(name, dn, key):
+    which, index = SEQ_BATCHES[key]
+    return seq_batch(name, dn, SEQ_BS[(name, tuple(dn))][which], index)
+
+
+@functools.lru_cache(maxsize=None)
+def seq_reference(name, dn, key, matryoshka=False):
+    """reference() for batch `key` ("a1" .. "c2") of a sequence: computed once
+    and shared, do not modify.  With matryoshka the loss is that signature's."""
+    from sparse_coding_amd.models.matryoshka import MatryoshkaBatchTopKEncoder
+
+    loss = MatryoshkaBatchTopKEncoder.loss if matryoshka else case(name).sig.loss
+    models, x = seq_models(name, dn, "matryoshka" if matryoshka else None), seq_x(name, dn, key)
+    g64, l64, c64 = _grads(loss, models, x, torch.float64)
+    g32, l32, c32 = _grads(loss, models, x, torch.float32)
+    return {"g64": g64, "loss64": l64, "c64": c64, "g32": g32, "loss32": l32, "c32": c32}
+
+
+def seq_loss_depths(entry, B):
+    name, (d, n), _, variant = entry
+    depths = loss_depths(case(name), B, d, n)
+    if variant == "matryoshka":
+        depths["mse_levels"] = depths["loss"]  # a level's sum is as deep as the last one's
+    return depths
 
 
 # ---------------------------------------------------------------------------

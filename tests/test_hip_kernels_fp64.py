@@ -208,12 +208,16 @@ def _reverse_ref(shape):
 @variants
 @shapes
 def test_enc_fwd_reverse(variant, shape):
+    """mode 3: the code, sum |code| and the fired counts.  A reverse code is
+    negative where -b < pre < 0; such an element is active but has not fired
+    (fired counts c > 0 in every mode, as EnsembleResampler.observe does from
+    aux["c"] on the torch backend)."""
     ext = _ext()
     M, B, d, n = shape
     bk, prio, bn = variant
     inp = _inputs(shape)
     ref = _reverse_ref(shape)
-    assert (ref["c"] < 0).any() and (ref["c"] > 0).any()
+    assert ((ref["c"] < -ref["e"]) & ~ref["undecided"]).any() and ref["on"].any()
     W = g(inp["W"])
     _, inv = _inv_norms(ext, W)
     c = torch.full((M, B, n), float("nan"), device=DEV)
@@ -221,7 +225,7 @@ def test_enc_fwd_reverse(variant, shape):
     lp, fired = g(lp0), g(fired0)
     ext.enc_fwd(g(inp["x"]), W, g(inp["bias"]), inv, c, lp, fired, 3, bk, prio, bn)
     st = R.check("code", c, ref["c"], ref["e"], ref["undecided"])
-    lo, hi = R.fired_range(ref["on"], ref["undecided"], fired0)
+    lo, hi = R.fired_range(ref["on"], ref["fired_undecided"], fired0)
     R.check_counts("fired", fired, lo, hi)
     st_l = R.sum_check("l1 = sum|code|", lp[:, 1], lp0[:, 1], ref["c"].abs(), ref["e"],
                        R.epi_sum_depth(B, n, bn), (1, 2), slack=ref["flip"].sum(dim=(1, 2)))

@@ -307,6 +307,11 @@ def test_forward_references_accept_fp32_signature_code():
         got = R.enc_reverse(x, W, inp["bias"])
     assert (ref["c"] < 0).any()
     R.check("reverse", got["c"], ref["c"], ref["e"], ref["undecided"])
+    # fired counts c > 0: the fp32 count lies in the range, the count of c != 0 does not
+    lo, hi = R.fired_range(ref["on"], ref["fired_undecided"], torch.full((M, 36), 3.0))
+    R.check_counts("reverse fired", 3.0 + (got["c"] > 0).float().sum(dim=1), lo, hi)
+    with pytest.raises(R.Mismatch):
+        R.check_counts("reverse fired", 3.0 + (got["c"] != 0).float().sum(dim=1), lo, hi)
 
     c = torch.clamp(inp["xm"][..., :1] * torch.randn(M, 33, 36, generator=gen), min=0.0)
     ref = R.dec(c, W, x)

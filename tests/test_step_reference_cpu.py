@@ -1,6 +1,8 @@
 """The step-gradient reference validated on the CPU (tests/step_reference.py).
 
-What test_hip_step_grads_gpu.py relies on is checked here without a GPU:
+What test_hip_step_grads_gpu.py and test_hip_step_sequence_gpu.py (the
+sequences: one pair of models, batches of changing size) rely on is checked
+here without a GPU:
 the seeds give inputs on which no nonsmooth decision is near its knee, the
 comparator accepts the fp32 yardstick and rejects the fp32 gradients of
 deliberately wrong problems, the recorder flags a planted near-knee argument,
@@ -53,6 +55,104 @@ def test_seeds_are_the_first_clean_ones():
     reference: nothing about a seed is a choice."""
     for name, shape, _ in R.GRID:
         assert R.first_clean_seed(name, shape) == R.SEEDS[(name, shape)], (name, shape)
+
+
+SEQ_IDS = [R.seq_id(e) for e in R.SEQ_GRID]
+
+
+def _seq_batches(entry):
+    """[(key, B, index)] of a sequence's six batches."""
+    return [(key, entry[2][which], index) for key, (which, index) in R.SEQ_BATCHES.items()]
+
+
+def test_every_case_has_a_sequence():
+    """Every case at its row of sizes, the aligned and "pre" rows, and the
+    sparse chain and Matryoshka variants, spelled out."""
+    plain = {(n, dn, Bs) for n, dn, Bs, v in R.SEQ_GRID if v is None}
+    for c in R.cases():
+        row = ((20, 132), (36, 17, 40)) if c.name in R.DEEP else ((68, 260), (132, 37, 260))
+        assert (c.name,) + row in plain, c.name
+    for name in ("tied", "topk", "batch_topk"):
+        assert (name, (64, 128), (128, 37, 256)) in plain
+    assert len(plain) == len(R.cases()) + 3
+    assert [e for e in R.SEQ_GRID if e[3] is not None] == [
+        ("tied", (68, 132), (132, 37, 136), "pre"),
+        ("untied", (68, 132), (132, 37, 136), "pre"),
+        ("masked_tied", (68, 132), (132, 37, 136), "pre"),
+        ("topk", (68, 260), (132, 37, 260), "sparse"),
+        ("batch_topk", (68, 260), (132, 37, 260), "sparse"),
+        ("batch_topk", (68, 260), (132, 37, 260), "matryoshka"),
+    ]
+    # the sizes do what they are there for
+    for _, (d, n), (Ba, Bb, Bc), v in R.SEQ_GRID:
+        assert Bb % 2 == 1 and Bb < 128 and Bc > Ba > Bb
+        if v == "pre":
+            assert Ba % 4 == 0 and Bc % 4 == 0
+    assert all(B % 128 == 0 and d % 32 == 0 and n % 128 == 0 for (d, n), (B, _, _) in [R.SEQ_ALIGNED])
+    # six batches, twelve calls; every batch is run, and every size is left and come back to
+    assert [k for k, _ in R.SEQ_CALLS] == "a1 a2 a3 a1 b1 c1 c2 c1 a2 a3 a1 a2".split()
+    assert {k for k, _ in R.SEQ_CALLS} == set(R.SEQ_BATCHES)
+    # the table holds the batches of the grid and nothing else
+    keys = {(e[0], e[1], B, i) for e in R.SEQ_GRID for _, B, i in _seq_batches(e)}
+    assert keys == set(R.SEQ_SEEDS)
+
+
+def test_sequence_shares_its_models_and_draws_distinct_batches():
+    for entry in R.SEQ_GRID:
+        name, dn, Bs, variant = entry
+        models = R.seq_models(name, dn, variant)
+        built, _ = R.build(name, (2, Bs[0]) + dn)
+        for (p, b), (p0, b0) in zip(models, built):
+            for (path, t), (_, t0) in zip(R.tree_items(p), R.tree_items(p0)):
+                assert torch.equal(t, t0), (name, path)
+            assert set(b) - set(b0) == ({"group_ends"} if variant == "matryoshka" else set())
+        xs = {key: R.seq_x(name, dn, key) for key in R.SEQ_BATCHES}
+        assert [x.shape[0] for x in xs.values()] == [Bs[0]] * 3 + [Bs[1]] + [Bs[2]] * 2
+        rows = torch.cat(list(xs.values()))
+        assert torch.unique(rows, dim=0).shape[0] == rows.shape[0], name  # no row twice, within or across batches
+
+
+@pytest.mark.parametrize("entry", R.SEQ_GRID, ids=SEQ_IDS)
+def test_seq_batches_are_clean(entry):
+    """Zero near-knee arguments on every batch of every sequence."""
+    name, dn, _, _ = entry
+    for key, B, index in _seq_batches(entry):
+        dec = R.seq_decisions(name, dn, B, index)
+        print(f"[seq64] {R.seq_id(entry)} {key} seed={R.SEQ_SEEDS[(name, dn, B, index)]} near={dec['near']} "
+              f"margin={dec['margin']:.2e}")
+        assert dec["near"] == 0, key
+
+
+def test_seq_seeds_are_the_first_clean_ones():
+    for name, dn, B, index in R.SEQ_SEEDS:
+        assert R.first_clean_seed(name, dn, batch=(B, index)) == R.SEQ_SEEDS[(name, dn, B, index)], \
+            (name, dn, B, index)
+    # the search stops at its limit
+    with pytest.raises(RuntimeError, match="no clean seed below 2"):
+        R.first_clean_seed("reverse", (68, 260), limit=2, batch=(260, 1))
+
+
+@pytest.mark.parametrize("entry", R.SEQ_GRID, ids=SEQ_IDS)
+def test_comparator_accepts_the_yardstick_on_every_sequence_batch(entry):
+    """As test_comparator_accepts_the_yardstick, after the one step from zero
+    state that the sequence test compares at."""
+    name, (d, n), _, variant = entry
+    c = R.case(name)
+    masked = (n, c.dict_sizes(n)) if c.dict_sizes else None
+    for key, B, _ in _seq_batches(entry):
+        ref = R.seq_reference(name, (d, n), key, variant == "matryoshka")
+        assert ref["c64"].shape == (2, B, n)
+        mu, nu = R.moments(ref["g32"], 1)
+        r_mu = R.compare(mu, ref["g64"], ref["g32"], "mu", 1, masked)
+        r_nu = R.compare(nu, ref["g64"], ref["g32"], "nu", 1, masked)
+        assert max(r_mu.values()) <= 1.0 and max(r_nu.values()) <= 1.0
+        R.compare_codes(ref["c32"], ref, masked[1] if masked else None)
+        ratios = R.compare_losses(ref["loss32"], ref, R.seq_loss_depths(entry, B))
+        assert set(ratios) == set(ref["loss64"]) - {"threshold"}
+        # the fired counts the GPU test demands are those of the float64 forward
+        assert torch.equal((ref["c32"] > 0).sum(1), (ref["c64"] > 0).sum(1)), key
+    if variant == "matryoshka":
+        assert "mse_levels" in ref["loss64"] and ref["loss64"]["mse_levels"].shape == (2, 3)
 
 
 def _stacked(name, shape):
