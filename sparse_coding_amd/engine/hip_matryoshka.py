@@ -21,7 +21,9 @@ class HipMatryoshkaStep(HipBatchTopKStep):
     ``topk_chain`` says: the nested losses come out of the sparse decode's
     running accumulator at the level boundaries, and a dense chain would pay
     one decode GEMM and its backward per level.  So it serves
-    d <= ext.sparse_max_d() and raises at allocation beyond that.
+    d <= ext.sparse_max_d() (8192) and raises at allocation beyond that; above
+    d = 2048 the same two launchers run k_wsparse_dec_gc, k_sparse_hit_lists
+    and k_wsparse_grad_w, which split a row over a workgroup's waves.
 
     ``R`` [M, G, B, d] holds, after a step, the suffix sums S_g of the prefix
     residuals (what feature j's gradient sees where the plain chain has r);

@@ -1139,7 +1139,9 @@ class HipTopKStep(_HipStep):
     visit only the hits ``c > 0`` of the same dense ``c`` and produce the same
     ``r``, ``loss_parts[:, 0]`` and ``gw``; codes, fired counts, the
     announced gradient and graph capture are the dense chain's.  It serves
-    d <= ext.sparse_max_d() and raises at allocation beyond that.
+    d <= ext.sparse_max_d() (8192) and raises at allocation beyond that; above
+    d = 2048 the launchers run the wide kernels (k_wsparse_dec_gc,
+    k_sparse_hit_lists, k_wsparse_grad_w: one launch more, no host read).
     """
 
     EPS = 1e-30  # un-clamped normalization (reference divides by the raw norm)

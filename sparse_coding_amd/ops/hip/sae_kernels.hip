@@ -79,7 +79,9 @@
 //   k_sparse_dec_gc / k_sparse_grad_w (the TopK family's chain behind the
 //   selection over the hits c > 0 alone; no GEMM, see the end of this file),
 //   k_msparse_dec_gc / k_msparse_grad_w (that chain with G nested prefix
-//   losses: Matryoshka BatchTopK)
+//   losses: Matryoshka BatchTopK); both pairs serve d <= 2048, and
+//   k_wsparse_dec_gc / k_sparse_hit_lists / k_wsparse_grad_w (sae_wsparse.hip)
+//   serve 2048 < d <= 8192 for both
 
 #include <hip/hip_runtime.h>
 
@@ -1834,6 +1836,8 @@ void k_gc2_t(const float* __restrict__ rT,       // [M, d, B]
 // element lane + 64 i in register i, so every row of W, r and x is read as DL
 // coalesced 256-byte loads.  DL is a template parameter, instantiated at the
 // depths SPARSE_DISPATCH_DL (sae_ops.hip) lists; d <= 64 * 32 = SPARSE_MAX_D.
+// A wider d goes to the kernels of sae_wsparse.hip, which split the vector over
+// a workgroup's waves.
 // No float atomics feed r, gpre or gw, and every sum has an order fixed by the
 // inputs alone: the three are reproducible bit for bit.
 //
@@ -2078,11 +2082,11 @@ struct SgwHit {
 template <int DL>
 SPK_DEV void sgw_load(SgwHit<DL>& h, int b, const float* __restrict__ ccol,
                       const float* __restrict__ gcol, const float* __restrict__ r_m,
-                      const float* __restrict__ x_m, float gscale, int n, int d, int lane) {
+                      const float* __restrict__ x_m, float gscale, int n, int ld, int d, int lane) {
   h.a = gscale * ccol[(long)b * n];
   h.g = gcol[(long)b * n];
-  const float* rr = r_m + (long)b * d;
-  const float* xr = x_m + (long)b * d;
+  const float* rr = r_m + (long)b * ld;
+  const float* xr = x_m + (long)b * ld;
 #pragma unroll
   for (int i = 0; i < DL; ++i) {
     const int col = lane + i * WAVE;
@@ -2100,12 +2104,14 @@ SPK_DEV void sgw_apply(float (&acc)[DL], const SgwHit<DL>& h) {
   }
 }
 
-// acc = sum over list[lo .. hi), ascending
+// acc = sum over list[lo .. hi), ascending.  The rows of r_m and x_m are ld
+// floats apart and d columns of them are read: ld = d for whole rows, and a
+// window of columns (k_wsparse_grad_w) has its base moved and d its width.
 template <int DL>
 SPK_DEV void sgw_accum(float (&acc)[DL], const int* list, int lo, int hi,
                        const float* __restrict__ ccol, const float* __restrict__ gcol,
                        const float* __restrict__ r_m, const float* __restrict__ x_m,
-                       float gscale, int n, int d, int lane) {
+                       float gscale, int n, int ld, int d, int lane) {
 #pragma unroll
   for (int i = 0; i < DL; ++i) acc[i] = 0.f;
   int h = lo;
@@ -2113,14 +2119,14 @@ SPK_DEV void sgw_accum(float (&acc)[DL], const int* list, int lo, int hi,
     const int b0 = __builtin_amdgcn_readfirstlane(list[h]);
     const int b1 = __builtin_amdgcn_readfirstlane(list[h + 1]);
     SgwHit<DL> h0, h1;
-    sgw_load<DL>(h0, b0, ccol, gcol, r_m, x_m, gscale, n, d, lane);
-    sgw_load<DL>(h1, b1, ccol, gcol, r_m, x_m, gscale, n, d, lane);
+    sgw_load<DL>(h0, b0, ccol, gcol, r_m, x_m, gscale, n, ld, d, lane);
+    sgw_load<DL>(h1, b1, ccol, gcol, r_m, x_m, gscale, n, ld, d, lane);
     sgw_apply<DL>(acc, h0);
     sgw_apply<DL>(acc, h1);
   }
   if (h < hi) {
     SgwHit<DL> h0;
-    sgw_load<DL>(h0, __builtin_amdgcn_readfirstlane(list[h]), ccol, gcol, r_m, x_m, gscale, n, d, lane);
+    sgw_load<DL>(h0, __builtin_amdgcn_readfirstlane(list[h]), ccol, gcol, r_m, x_m, gscale, n, ld, d, lane);
     sgw_apply<DL>(acc, h0);
   }
 }
@@ -2196,7 +2202,7 @@ void k_sparse_grad_w(const float* __restrict__ c,     // [M, B, n]
     const int count = tot[f];
     if (count > SGW_LIGHT) continue;
     sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, 0, count, c_m + j, g_m + j, r_m, x_m,
-                  gscale, n, d, lane);
+                  gscale, n, d, d, lane);
 #pragma unroll
     for (int i = 0; i < DL; ++i) {
       const int col = lane + i * WAVE;
@@ -2212,7 +2218,7 @@ void k_sparse_grad_w(const float* __restrict__ c,     // [M, B, n]
     const int per = (count + SGW_NW - 1) / SGW_NW;
     const int lo = spk_min(count, wave * per), hi = spk_min(count, lo + per);
     sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, lo, hi, c_m + j, g_m + j, r_m, x_m,
-                  gscale, n, d, lane);
+                  gscale, n, d, d, lane);
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
 #pragma unroll
@@ -2452,7 +2458,7 @@ void k_msparse_grad_w(const float* __restrict__ c,     // [M, B, n]
     const int count = tot[f];
     if (count > SGW_LIGHT) continue;
     sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, 0, count, c_m + j, g_m + j,
-                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, d, lane);
+                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, d, d, lane);
 #pragma unroll
     for (int i = 0; i < DL; ++i) {
       const int col = lane + i * WAVE;
@@ -2468,7 +2474,7 @@ void k_msparse_grad_w(const float* __restrict__ c,     // [M, B, n]
     const int per = (count + SGW_NW - 1) / SGW_NW;
     const int lo = spk_min(count, wave * per), hi = spk_min(count, lo + per);
     sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, lo, hi, c_m + j, g_m + j,
-                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, d, lane);
+                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, d, d, lane);
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
 #pragma unroll

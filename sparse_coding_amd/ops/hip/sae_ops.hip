@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "sae_kernels.hip"
+#include "sae_wsparse.hip"
 
 static inline void check_in(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
@@ -434,8 +435,10 @@ void batch_topk_select(torch::Tensor scores, torch::Tensor c_out, torch::Tensor 
 // The sparse TopK chain (k_sparse_dec_gc / k_sparse_grad_w).  Both kernels are
 // templates over DL, the registers a lane holds of one length-d vector; the
 // launchers take the smallest compiled DL >= ceil(d / 64).  The second template
-// argument is the kernel's minimum waves per SIMD.
-int64_t sparse_max_d() { return SPARSE_MAX_D; }
+// argument is the kernel's minimum waves per SIMD.  That serves
+// d <= SPARSE_MAX_D; above it and up to WSPARSE_MAX_D every launcher branches,
+// ahead of the depth dispatch, to the wide kernels of sae_wsparse.hip.
+int64_t sparse_max_d() { return WSPARSE_MAX_D; }
 
 // int32 elements of the hit-list workspace sparse_grad_w needs: [M, n, B]
 int64_t sparse_hits_size(int64_t M, int64_t B, int64_t n) { return M * n * B; }
@@ -462,14 +465,44 @@ static SparseShape sparse_shape(const char* who, const torch::Tensor& c, const t
                                 const torch::Tensor& r, const torch::Tensor& x) {
   TORCH_CHECK(c.dim() == 3 && r.dim() == 3, who, ": c must be [M,B,n] and r [M,B,d]");
   const long M = c.size(0), B = c.size(1), n = c.size(2), d = r.size(2);
-  TORCH_CHECK(d >= 1 && d <= SPARSE_MAX_D, who, ": d = ", d, " is outside the sparse chain's range 1..",
-              SPARSE_MAX_D);
+  TORCH_CHECK(d >= 1 && d <= WSPARSE_MAX_D, who, ": d = ", d, " is outside the sparse chain's range 1..",
+              WSPARSE_MAX_D);
   TORCH_CHECK(gpre.sizes() == c.sizes(), who, ": gpre must have the shape of c");
   TORCH_CHECK(r.size(0) == M && r.size(1) == B, who, ": r must be [M,B,d]");
   TORCH_CHECK(x.size(-1) == d && x.size(x.dim() - 2) == B && (x.dim() == 2 || x.dim() == 3),
               who, ": x must be [B,d] or [M,B,d]");
   TORCH_CHECK(M <= 65535 && B < (1L << 31) && n < (1L << 31), who, ": M, B or n too large");
   return {(int)M, (int)B, (int)n, (int)d, x_model_stride(x, (int)M)};
+}
+
+// The wide decode (d > SPARSE_MAX_D) of both chains: the plain one is G = 1
+// with R = r and its loss at stride 2.
+static void wsparse_dec_gc_launch(const SparseShape& s, const torch::Tensor& c, const torch::Tensor& W,
+                                  const torch::Tensor& inv_norms, const torch::Tensor& x,
+                                  const int* ends_p, int G, torch::Tensor& R, torch::Tensor& gpre,
+                                  torch::Tensor& parts, int parts_stride) {
+  dim3 grid(s.B, s.M);
+#define LAUNCH_WSDG(DLW)                                                                      \
+  hipLaunchKernelGGL((k_wsparse_dec_gc<DLW, 4>), grid, dim3(WSP_T), 0, cur_stream(),          \
+                     c.data_ptr<float>(), W.data_ptr<float>(), inv_norms.data_ptr<float>(),   \
+                     x.data_ptr<float>(), ends_p, R.data_ptr<float>(), gpre.data_ptr<float>(), \
+                     parts.data_ptr<float>(), s.B, s.d, s.n, G, s.x_mstride, parts_stride)
+  if (s.d <= 8 * WSP_T) LAUNCH_WSDG(8);
+  else LAUNCH_WSDG(16);
+#undef LAUNCH_WSDG
+}
+
+// The wide weight gradient of both chains: the hit lists in a launch of their
+// own, then one workgroup per strip of 64 features and window of 1024 columns.
+static void wsparse_grad_w_launch(const SparseShape& s, const torch::Tensor& c, const torch::Tensor& gpre,
+                                  const torch::Tensor& R, const torch::Tensor& x, const int* ends_p,
+                                  int G, torch::Tensor& gw, int* hits_p, int* counts_p) {
+  hipLaunchKernelGGL(k_sparse_hit_lists, dim3(cdiv(s.n, SGW_STRIP), s.M), dim3(SGW_T), 0,
+                     cur_stream(), c.data_ptr<float>(), hits_p, counts_p, s.B, s.n);
+  hipLaunchKernelGGL(k_wsparse_grad_w, dim3(cdiv(s.n, SGW_STRIP), cdiv(s.d, WSGW_CHUNK), s.M),
+                     dim3(SGW_T), 0, cur_stream(), c.data_ptr<float>(), gpre.data_ptr<float>(),
+                     R.data_ptr<float>(), x.data_ptr<float>(), ends_p, gw.data_ptr<float>(),
+                     (const int*)hits_p, (const int*)counts_p, s.B, s.d, s.n, G, s.x_mstride);
 }
 
 void sparse_dec_gc(torch::Tensor c, torch::Tensor W, torch::Tensor inv_norms, torch::Tensor x,
@@ -482,6 +515,8 @@ void sparse_dec_gc(torch::Tensor c, torch::Tensor W, torch::Tensor inv_norms, to
   TORCH_CHECK(inv_norms.numel() == (long)s.M * s.n, "sparse_dec_gc: inv_norms must be [M,n]");
   TORCH_CHECK(loss_parts.numel() == (long)s.M * 2, "sparse_dec_gc: loss_parts must be [M,2]");
   if (s.M == 0 || s.B == 0) return;
+  if (s.d > SPARSE_MAX_D)
+    return wsparse_dec_gc_launch(s, c, W, inv_norms, x, nullptr, 1, r, gpre, loss_parts, 2);
   dim3 grid(cdiv(s.B, SDG_T / WAVE), s.M);
 #define LAUNCH_SDG(DL)                                                                        \
   hipLaunchKernelGGL((k_sparse_dec_gc<DL, (DL <= 16 ? 8 : 2)>), grid, dim3(SDG_T), 0,         \
@@ -505,6 +540,8 @@ void sparse_grad_w(torch::Tensor c, torch::Tensor gpre, torch::Tensor r, torch::
   int* hits_p = int32_ptr(hits, "hits");
   int* counts_p = int32_ptr(hit_counts, "hit_counts");
   if (s.M == 0 || s.n == 0) return;
+  if (s.d > SPARSE_MAX_D)
+    return wsparse_grad_w_launch(s, c, gpre, r, x, nullptr, 1, gw, hits_p, counts_p);
   dim3 grid(cdiv(s.n, SGW_STRIP), s.M);
 #define LAUNCH_SGW(DL)                                                                        \
   hipLaunchKernelGGL((k_sparse_grad_w<DL, (DL <= 16 ? 4 : 2)>), grid, dim3(SGW_T), 0,         \
@@ -543,6 +580,8 @@ void msparse_dec_gc(torch::Tensor c, torch::Tensor W, torch::Tensor inv_norms, t
               "msparse_dec_gc: mse_parts must be [M,G]");
   const int* ends_p = int32_ptr(ends, "ends");
   if (s.M == 0 || s.B == 0) return;
+  if (s.d > SPARSE_MAX_D)
+    return wsparse_dec_gc_launch(s, c, W, inv_norms, x, ends_p, G, R, gpre, mse_parts, G);
   dim3 grid(cdiv(s.B, SDG_T / WAVE), s.M);
 #define LAUNCH_MSDG(DL)                                                                       \
   hipLaunchKernelGGL((k_msparse_dec_gc<DL, (DL <= 12 ? 8 : DL <= 16 ? 4 : 2)>), grid,         \
@@ -570,6 +609,8 @@ void msparse_grad_w(torch::Tensor c, torch::Tensor gpre, torch::Tensor R, torch:
   int* hits_p = int32_ptr(hits, "hits");
   int* counts_p = int32_ptr(hit_counts, "hit_counts");
   if (s.M == 0 || s.n == 0) return;
+  if (s.d > SPARSE_MAX_D)
+    return wsparse_grad_w_launch(s, c, gpre, R, x, ends_p, G, gw, hits_p, counts_p);
   dim3 grid(cdiv(s.n, SGW_STRIP), s.M);
 #define LAUNCH_MSGW(DL)                                                                       \
   hipLaunchKernelGGL((k_msparse_grad_w<DL, (DL <= 16 ? 4 : 2)>), grid, dim3(SGW_T), 0,        \
@@ -665,7 +706,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("thr_out"), py::arg("work"),
         py::arg("threshold") = py::none(), py::arg("threshold_n") = py::none(),
         py::arg("threshold_lr") = py::none());
-  m.def("sparse_max_d", &sparse_max_d, "largest d the sparse TopK chain serves");
+  m.def("sparse_max_d", &sparse_max_d, "largest d the sparse TopK and Matryoshka chains serve");
   m.def("sparse_hits_size", &sparse_hits_size, "int32 elements of sparse_grad_w's hit-list workspace",
         py::arg("M"), py::arg("B"), py::arg("n"));
   m.def("sparse_dec_gc", &sparse_dec_gc,

@@ -33,7 +33,7 @@ behind the selection:
   topk_chain="dense"   dec_fwd, gc and two grad_w GEMMs over the full [M, B, n]
                        code matrix (default)
   topk_chain="sparse"  k_sparse_dec_gc + k_sparse_grad_w, which visit only the
-                       hits c > 0; d <= 2048.  Opt-in: measured in
+                       hits c > 0; d <= 8192.  Opt-in: measured in
                        profiles/README.md, the default is a later decision
 
 Defaults come from env (SC_AMD_BK / SC_AMD_PRIO / SC_AMD_STAGING /
