@@ -115,12 +115,15 @@ def maybe_make_step(ensemble, required: bool = False) -> Optional["_HipStep"]:
     from sparse_coding_amd.models.positive import FunctionalPositiveTiedSAE
     from sparse_coding_amd.models.semilinear import SemiLinearSAE
     from sparse_coding_amd.models.topk import TopKEncoder
+    from sparse_coding_amd.engine.hip_auxk import HipTopKAuxStep
+    from sparse_coding_amd.models.topk_auxk import TopKAuxEncoder
 
     def sae(**flags):
         return lambda ens, ext: HipSAEStep(ens, ext, **flags)
 
     make = {
         TopKEncoder: HipTopKStep,
+        TopKAuxEncoder: HipTopKAuxStep,
         BatchTopKEncoder: HipBatchTopKStep,
         MatryoshkaBatchTopKEncoder: HipMatryoshkaStep,
         sigs.FunctionalThresholdingSAE: HipThresholdStep,

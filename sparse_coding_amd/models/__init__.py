@@ -8,6 +8,7 @@ from sparse_coding_amd.models.sae_signatures import (
     FunctionalMaskedSAE, FunctionalReverseSAE,
 )
 from sparse_coding_amd.models.topk import TopKEncoder, TopKLearnedDict
+from sparse_coding_amd.models.topk_auxk import TopKAuxEncoder
 from sparse_coding_amd.models.batch_topk import BatchTopKEncoder, BatchTopKLearnedDict
 from sparse_coding_amd.models.matryoshka import (
     MatryoshkaBatchTopKEncoder, MatryoshkaBatchTopKLearnedDict,

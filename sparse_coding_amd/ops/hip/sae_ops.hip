@@ -7,6 +7,7 @@
 
 #include "sae_kernels.hip"
 #include "sae_wsparse.hip"
+#include "sae_auxk.hip"
 
 static inline void check_in(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
@@ -621,6 +622,151 @@ void msparse_grad_w(torch::Tensor c, torch::Tensor gpre, torch::Tensor R, torch:
 #undef LAUNCH_MSGW
 }
 
+// The AuxK chain of the TopK step (sae_auxk.hip).  Per model: ages [n] int32,
+// dead_after, k_aux and n_dead int32, alpha fp32.  The row lists aux_idx /
+// aux_val / gpre_aux are [M, B, KA] with KA >= max k_aux, aux_cnt is [M, B].
+int64_t auxk_max_d() { return AUXK_MAX_D; }
+
+static void auxk_models(const char* who, long M, const torch::Tensor& a, const char* name) {
+  TORCH_CHECK(a.numel() == M, who, ": ", name, " must be [M]");
+}
+
+struct AuxkLists {
+  int M, B, KA;
+  int* idx;
+  float* val;
+  int* cnt;
+};
+
+static AuxkLists auxk_lists(const char* who, const torch::Tensor& aux_idx, const torch::Tensor& aux_val,
+                            const torch::Tensor& aux_cnt) {
+  check_in(aux_val, "aux_val");
+  TORCH_CHECK(aux_idx.dim() == 3 && aux_val.sizes() == aux_idx.sizes(), who,
+              ": aux_idx and aux_val must be [M,B,KA]");
+  const long M = aux_idx.size(0), B = aux_idx.size(1), KA = aux_idx.size(2);
+  TORCH_CHECK(KA >= 1 && KA <= AUXK_MAX_KA, who, ": KA = ", KA, " is outside 1..", AUXK_MAX_KA);
+  TORCH_CHECK(aux_cnt.dim() == 2 && aux_cnt.size(0) == M && aux_cnt.size(1) == B, who,
+              ": aux_cnt must be [M,B]");
+  TORCH_CHECK(M <= 65535 && B < (1L << 31), who, ": M or B too large");
+  return {(int)M, (int)B, (int)KA, int32_ptr(aux_idx, "aux_idx"), aux_val.data_ptr<float>(),
+          int32_ptr(aux_cnt, "aux_cnt")};
+}
+
+void auxk_age(torch::Tensor ages, c10::optional<torch::Tensor> hit_counts, torch::Tensor dead_after,
+              torch::Tensor n_dead) {
+  TORCH_CHECK(ages.dim() == 2, "auxk_age: ages must be int32 [M,n]");
+  const long M = ages.size(0), n = ages.size(1);
+  auxk_models("auxk_age", M, dead_after, "dead_after");
+  auxk_models("auxk_age", M, n_dead, "n_dead");
+  TORCH_CHECK(M <= 65535 && n < (1L << 31), "auxk_age: M or n too large");
+  const int* hc_p = nullptr;
+  if (hit_counts.has_value()) {
+    TORCH_CHECK(hit_counts->numel() == M * n, "auxk_age: hit_counts must be [M,n]");
+    hc_p = int32_ptr(*hit_counts, "hit_counts");
+  }
+  int* ages_p = int32_ptr(ages, "ages");
+  const int* da_p = int32_ptr(dead_after, "dead_after");
+  int* nd_p = int32_ptr(n_dead, "n_dead");
+  if (M == 0) return;
+  hipLaunchKernelGGL(k_auxk_age, dim3(M), dim3(AXA_T), 0, cur_stream(), ages_p, hc_p, da_p, nd_p,
+                     (int)n, hc_p ? 1 : 0);
+}
+
+void auxk_select(torch::Tensor scores, torch::Tensor ages, torch::Tensor dead_after, torch::Tensor k_aux,
+                 torch::Tensor n_dead, torch::Tensor aux_idx, torch::Tensor aux_val, torch::Tensor aux_cnt) {
+  CHECK_IN(scores);
+  const AuxkLists l = auxk_lists("auxk_select", aux_idx, aux_val, aux_cnt);
+  TORCH_CHECK(scores.dim() == 3 && scores.size(0) == l.M && scores.size(1) == l.B,
+              "auxk_select: scores must be [M,B,n]");
+  const long n = scores.size(2);
+  TORCH_CHECK(n >= 1 && n < (1L << 31), "auxk_select: n out of range");
+  TORCH_CHECK(ages.numel() == l.M * n, "auxk_select: ages must be [M,n]");
+  auxk_models("auxk_select", l.M, dead_after, "dead_after");
+  auxk_models("auxk_select", l.M, k_aux, "k_aux");
+  auxk_models("auxk_select", l.M, n_dead, "n_dead");
+  const int* ages_p = int32_ptr(ages, "ages");
+  const int* da_p = int32_ptr(dead_after, "dead_after");
+  const int* ka_p = int32_ptr(k_aux, "k_aux");
+  const int* nd_p = int32_ptr(n_dead, "n_dead");
+  if (l.M == 0 || l.B == 0) return;
+  hipLaunchKernelGGL(k_auxk_select, dim3(l.B, l.M), dim3(AXS_T), 0, cur_stream(),
+                     scores.data_ptr<float>(), ages_p, da_p, ka_p, nd_p, l.idx, l.val, l.cnt, l.B, (int)n,
+                     l.KA);
+}
+
+void auxk_dec_gc(torch::Tensor aux_idx, torch::Tensor aux_val, torch::Tensor aux_cnt, torch::Tensor W,
+                 torch::Tensor inv_norms, torch::Tensor r, torch::Tensor alpha, torch::Tensor k_aux,
+                 torch::Tensor n_dead, torch::Tensor r_aux, torch::Tensor gpre_aux,
+                 torch::Tensor loss_parts) {
+  CHECK_IN(W); CHECK_IN(inv_norms); CHECK_IN(r); CHECK_IN(alpha); CHECK_IN(r_aux); CHECK_IN(gpre_aux);
+  CHECK_IN(loss_parts);
+  const AuxkLists l = auxk_lists("auxk_dec_gc", aux_idx, aux_val, aux_cnt);
+  TORCH_CHECK(W.dim() == 3 && W.size(0) == l.M, "auxk_dec_gc: W must be [M,n,d]");
+  const long n = W.size(1), d = W.size(2);
+  TORCH_CHECK(d >= 1 && d <= AUXK_MAX_D, "auxk_dec_gc: d = ", d, " is outside the AuxK chain's range 1..",
+              AUXK_MAX_D);
+  TORCH_CHECK(n >= 1 && n < (1L << 31), "auxk_dec_gc: n out of range");
+  TORCH_CHECK(r.dim() == 3 && r.size(0) == l.M && r.size(1) == l.B && r.size(2) == d &&
+              r_aux.sizes() == r.sizes(), "auxk_dec_gc: r and r_aux must be [M,B,d]");
+  TORCH_CHECK(gpre_aux.sizes() == aux_idx.sizes(), "auxk_dec_gc: gpre_aux must be [M,B,KA]");
+  TORCH_CHECK(inv_norms.numel() == l.M * n, "auxk_dec_gc: inv_norms must be [M,n]");
+  TORCH_CHECK(loss_parts.numel() == (long)l.M * 2, "auxk_dec_gc: loss_parts must be [M,2]");
+  auxk_models("auxk_dec_gc", l.M, alpha, "alpha");
+  auxk_models("auxk_dec_gc", l.M, k_aux, "k_aux");
+  auxk_models("auxk_dec_gc", l.M, n_dead, "n_dead");
+  const int* ka_p = int32_ptr(k_aux, "k_aux");
+  const int* nd_p = int32_ptr(n_dead, "n_dead");
+  if (l.M == 0 || l.B == 0) return;
+  dim3 grid(cdiv(l.B, SDG_T / WAVE), l.M);
+#define LAUNCH_AXDG(DL)                                                                       \
+  hipLaunchKernelGGL((k_auxk_dec_gc<DL, (DL <= 16 ? 8 : 2)>), grid, dim3(SDG_T), 0,           \
+                     cur_stream(), (const int*)l.idx, (const float*)l.val, (const int*)l.cnt, \
+                     W.data_ptr<float>(), inv_norms.data_ptr<float>(), r.data_ptr<float>(),   \
+                     alpha.data_ptr<float>(), ka_p, nd_p, r_aux.data_ptr<float>(),            \
+                     gpre_aux.data_ptr<float>(), loss_parts.data_ptr<float>(), l.B, (int)d,   \
+                     (int)n, l.KA)
+  SPARSE_DISPATCH_DL(d, LAUNCH_AXDG);
+#undef LAUNCH_AXDG
+}
+
+void auxk_grad_w(torch::Tensor aux_idx, torch::Tensor aux_val, torch::Tensor aux_cnt,
+                 torch::Tensor gpre_aux, torch::Tensor r_aux, torch::Tensor x, torch::Tensor ages,
+                 torch::Tensor dead_after, torch::Tensor k_aux, torch::Tensor n_dead, torch::Tensor alpha,
+                 torch::Tensor gw) {
+  CHECK_IN(gpre_aux); CHECK_IN(r_aux); CHECK_IN(x); CHECK_IN(alpha); CHECK_IN(gw);
+  const AuxkLists l = auxk_lists("auxk_grad_w", aux_idx, aux_val, aux_cnt);
+  TORCH_CHECK(gw.dim() == 3 && gw.size(0) == l.M, "auxk_grad_w: gw must be [M,n,d]");
+  const long n = gw.size(1), d = gw.size(2);
+  TORCH_CHECK(d >= 1 && d <= AUXK_MAX_D, "auxk_grad_w: d = ", d, " is outside the AuxK chain's range 1..",
+              AUXK_MAX_D);
+  TORCH_CHECK(n >= 1 && n < (1L << 31), "auxk_grad_w: n out of range");
+  TORCH_CHECK(r_aux.dim() == 3 && r_aux.size(0) == l.M && r_aux.size(1) == l.B && r_aux.size(2) == d,
+              "auxk_grad_w: r_aux must be [M,B,d]");
+  TORCH_CHECK(x.size(-1) == d && x.size(x.dim() - 2) == l.B && (x.dim() == 2 || x.dim() == 3),
+              "auxk_grad_w: x must be [B,d] or [M,B,d]");
+  TORCH_CHECK(gpre_aux.sizes() == aux_idx.sizes(), "auxk_grad_w: gpre_aux must be [M,B,KA]");
+  TORCH_CHECK(ages.numel() == l.M * n, "auxk_grad_w: ages must be [M,n]");
+  auxk_models("auxk_grad_w", l.M, dead_after, "dead_after");
+  auxk_models("auxk_grad_w", l.M, k_aux, "k_aux");
+  auxk_models("auxk_grad_w", l.M, n_dead, "n_dead");
+  auxk_models("auxk_grad_w", l.M, alpha, "alpha");
+  const int* ages_p = int32_ptr(ages, "ages");
+  const int* da_p = int32_ptr(dead_after, "dead_after");
+  const int* ka_p = int32_ptr(k_aux, "k_aux");
+  const int* nd_p = int32_ptr(n_dead, "n_dead");
+  const long x_mstride = x_model_stride(x, l.M);
+  if (l.M == 0 || l.B == 0) return;
+  dim3 grid(cdiv(n, SGW_STRIP), l.M);
+#define LAUNCH_AXGW(DL)                                                                       \
+  hipLaunchKernelGGL((k_auxk_grad_w<DL, (DL <= 16 ? 4 : 2)>), grid, dim3(SGW_T), 0,           \
+                     cur_stream(), (const int*)l.idx, (const float*)l.val, (const int*)l.cnt, \
+                     gpre_aux.data_ptr<float>(), r_aux.data_ptr<float>(), x.data_ptr<float>(), \
+                     ages_p, da_p, ka_p, nd_p, alpha.data_ptr<float>(), gw.data_ptr<float>(), \
+                     l.B, (int)d, (int)n, l.KA, x_mstride)
+  SPARSE_DISPATCH_DL(d, LAUNCH_AXGW);
+#undef LAUNCH_AXGW
+}
+
 void resample(torch::Tensor fired, torch::Tensor new_rows, torch::Tensor enc_scale,
               torch::Tensor W, torch::Tensor mu_w, torch::Tensor nu_w,
               c10::optional<torch::Tensor> dec,
@@ -726,6 +872,25 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "sparse_grad_w with a feature's residual rows read from its level of R",
         py::arg("c"), py::arg("gpre"), py::arg("R"), py::arg("x"), py::arg("ends"), py::arg("gw"),
         py::arg("hits"), py::arg("hit_counts"));
+  m.def("auxk_max_d", &auxk_max_d, "largest d the AuxK chain serves");
+  m.def("auxk_age", &auxk_age,
+        "without hit_counts: n_dead[m] = #(ages >= dead_after); with them: ages = 0 where hit, else + 1",
+        py::arg("ages"), py::arg("hit_counts"), py::arg("dead_after"), py::arg("n_dead"));
+  m.def("auxk_select", &auxk_select,
+        "per row the min(k_aux, n_dead) largest positive scores over the dead columns, compact and "
+        "ascending in column, the lowest columns first among equals",
+        py::arg("scores"), py::arg("ages"), py::arg("dead_after"), py::arg("k_aux"), py::arg("n_dead"),
+        py::arg("aux_idx"), py::arg("aux_val"), py::arg("aux_cnt"));
+  m.def("auxk_dec_gc", &auxk_dec_gc,
+        "r_aux = z @ What + r (+ its squares into loss_parts[:, 1]), gpre_aux at the lists' entries",
+        py::arg("aux_idx"), py::arg("aux_val"), py::arg("aux_cnt"), py::arg("W"), py::arg("inv_norms"),
+        py::arg("r"), py::arg("alpha"), py::arg("k_aux"), py::arg("n_dead"), py::arg("r_aux"),
+        py::arg("gpre_aux"), py::arg("loss_parts"));
+  m.def("auxk_grad_w", &auxk_grad_w,
+        "gw[j,:] += sum over the aux hit rows of gs val r_aux + gpre_aux x; no atomics",
+        py::arg("aux_idx"), py::arg("aux_val"), py::arg("aux_cnt"), py::arg("gpre_aux"), py::arg("r_aux"),
+        py::arg("x"), py::arg("ages"), py::arg("dead_after"), py::arg("k_aux"), py::arg("n_dead"),
+        py::arg("alpha"), py::arg("gw"));
   m.def("resample", &resample, "fused dead-neuron resample (K14): rank dead, rewrite rows, zero Adam state",
         py::arg("fired"), py::arg("new_rows"), py::arg("enc_scale"),
         py::arg("W"), py::arg("mu_w"), py::arg("nu_w"),
