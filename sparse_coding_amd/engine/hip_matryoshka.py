@@ -17,7 +17,7 @@ class HipMatryoshkaStep(HipBatchTopKStep):
 
     Row norms, the encoder GEMM, the batch-level selection, the threshold
     state, Adam and graph capture are HipBatchTopKStep's.  Behind the selection
-    it always runs k_msparse_dec_gc and k_msparse_grad_w, whatever
+    it always runs k_sparse_dec_gc and k_sparse_grad_w (LEVELS), whatever
     ``topk_chain`` says: the nested losses come out of the sparse decode's
     running accumulator at the level boundaries, and a dense chain would pay
     one decode GEMM and its backward per level.  So it serves

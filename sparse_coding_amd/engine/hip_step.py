@@ -25,8 +25,8 @@ hand-written gfx950 HIP kernels (``sparse_coding_amd/ops/hip/sae_kernels.hip``):
   k_topk_select  : per-row radix top-k + scatter (TopK)
   k_btk_hist/k_btk_write : batch-level radix top-k over many workgroups +
                    scatter + inference-threshold state (BatchTopK)
-  k_msparse_dec_gc/k_msparse_grad_w : the sparse chain with G nested prefix
-                   losses (Matryoshka BatchTopK)
+  k_sparse_dec_gc/k_sparse_grad_w with LEVELS : the sparse chain with G nested
+                   prefix losses (Matryoshka BatchTopK)
 
 Fused-step coverage: EVERY trainable signature in the zoo — tied, untied,
 masked tied/untied, thresholding, reverse, tied-centered, positive-tied,

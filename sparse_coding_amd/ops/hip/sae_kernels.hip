@@ -77,11 +77,11 @@
 //   batch-level radix top-k over many workgroups), k_resample (K14 on-device),
 //   k_lista_bwd_elem (one-pass LISTA backward elementwise chain),
 //   k_sparse_dec_gc / k_sparse_grad_w (the TopK family's chain behind the
-//   selection over the hits c > 0 alone; no GEMM, see the end of this file),
-//   k_msparse_dec_gc / k_msparse_grad_w (that chain with G nested prefix
-//   losses: Matryoshka BatchTopK); both pairs serve d <= 2048, and
+//   selection over the hits c > 0 alone; no GEMM, see the end of this file;
+//   their LEVELS instantiations are that chain with G nested prefix losses:
+//   Matryoshka BatchTopK); they serve d <= 2048, and
 //   k_wsparse_dec_gc / k_sparse_hit_lists / k_wsparse_grad_w (sae_wsparse.hip)
-//   serve 2048 < d <= 8192 for both
+//   serve 2048 < d <= 8192
 
 #include <hip/hip_runtime.h>
 
@@ -1857,12 +1857,16 @@ void k_gc2_t(const float* __restrict__ rT,       // [M, d, B]
 // contain no call: neither s_swappc nor v_pk_*_f32 occurs in their code.
 //
 // Registers and scratch per instantiation, from the gfx950 code object's
-// metadata (.vgpr_count / .private_segment_fixed_size); no variant spills:
+// metadata (.vgpr_count / .private_segment_fixed_size); no variant spills.  The
+// waves per SIMD are what the launch bounds ask for and the VGPR counts allow
+// (512 / VGPRs): derived from the metadata, not observed on a device.
 //
-//   DL                      1    2    4    8   12   16   32
-//   k_sparse_dec_gc  VGPRs  22   21   23   31   39   50  114   (8 waves/SIMD asked for; 2 at DL = 32)
-//   k_sparse_grad_w  VGPRs  26   30   44   70   98  128  243   (4 waves/SIMD asked for; 2 at DL = 32)
-//   scratch bytes (both)    0    0    0    0    0    0    0
+//   DL                              1    2    4    8   12   16   32
+//   k_sparse_dec_gc  plain  VGPRs   20   18   20   28   36   46   97   (8 waves/SIMD asked for; 2 at DL = 32)
+//   k_sparse_dec_gc  LEVELS VGPRs   26   24   27   38   52   71  182   (8 asked for; 4 at DL = 16, 2 at DL = 32)
+//   k_sparse_grad_w  plain  VGPRs   22   24   38   64   94  122  237   (4 waves/SIMD asked for; 2 at DL = 32)
+//   k_sparse_grad_w  LEVELS VGPRs   22   24   38   66   94  122  239   (as plain)
+//   scratch bytes (all)             0    0    0    0    0    0    0
 // ---------------------------------------------------------------------------
 #if defined(__HIP_DEVICE_COMPILE__)
 #define SPK_NOPK __attribute__((target("no-packed-fp32-ops")))
@@ -1900,26 +1904,135 @@ SPK_DEV void spk_barrier() {
 }
 // __threadfence()
 SPK_DEV void spk_fence_device() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "agent"); }
+// A helper is handed a kernel's __shared__ array as a pointer into the LDS
+// address space.  Through a plain reference the array is a generic pointer with
+// 64-bit indices until late in the compilation, and the constant part of an
+// address no longer folds into the ds instructions' offset field: the combine
+// of k_sparse_grad_w<16> then holds 16 addresses in registers and spills.
+#define SPK_LDS __attribute__((address_space(3)))
+template <class T>
+SPK_DEV SPK_LDS T* spk_lds(T* p) { return (SPK_LDS T*)p; }
+
+// ---------------------------------------------------------------------------
+// Levels.  Matryoshka BatchTopK (models/matryoshka.py) cuts the features into
+// G <= 8 levels by the ascending ends e_0 < ... < e_{G-1} = n (`ends`, int32
+// [M, G]), and its loss is the sum over g of mse(x, c[:, :e_g] @ What[:e_g]).
+// With r_g = c[:, :e_g] @ What[:e_g] - x the residual of prefix g and
+// S_g = r_g + ... + r_{G-1}, a feature j of level g(j) has
+//   gpre[b,j] = (gscale inv[j]) dot(S_g(j)[b,:], W[j,:])
+//   gw[j,:]   = sum over its hit rows b of gscale c[b,j] S_g(j)[b,:] + gpre[b,j] x[b,:]
+// which is the plain chain with S_g(j) where that has r, so no level costs a
+// GEMM and the plain chain is the case G = 1: R [M, G, B, d] is then r and
+// `ends` is not read.  The narrow kernels below are templates over LEVELS; at
+// false, G is the compile-time constant 1 and every level loop is one trip.
+//
+// R costs 3 G B d floats of traffic per model (r_g out, back in, S out; the
+// last level is not rewritten).  Ends outside 0..n or out of order are clamped
+// into an ascending sequence: a bad `ends` gives wrong levels, never a wild
+// address.  The last level always ends at n.
+// ---------------------------------------------------------------------------
+#define MSP_MAX_G 8
+
+// end of level g, clamped into [lo, n]; the last level ends at n
+SPK_DEV int msp_end(const int* __restrict__ ends_m, int g, int G, int lo, int n) {
+  if (g == G - 1) return n;
+  const int e = ends_m[g];
+  return e < lo ? lo : spk_min(e, n);
+}
+
+// the clamped ends again, from the top: level g is [returned lo, e1), and e1
+// of level g is lo of level g + 1
+SPK_DEV int msp_level_span(const int* __restrict__ ends_m, int g, int G, int n, int& e1) {
+  int lo = 0;
+  for (int h = 0; h < g; ++h) lo = msp_end(ends_m, h, G, lo, n);
+  e1 = msp_end(ends_m, g, G, lo, n);
+  return lo;
+}
+
+// R[m, g(j)]: the [B, d] block feature j's hits read their residual rows from.
+// g(j) counts the ends <= j, wave-uniform; a strip may straddle a boundary.
+SPK_DEV const float* msp_level_rows(const float* __restrict__ R_m, const int* __restrict__ ends_m,
+                                    int j, int G, int n, long level) {
+  int g = 0, lo = 0;
+  for (int h = 0; h < G - 1; ++h) {
+    lo = msp_end(ends_m, h, G, lo, n);
+    g += lo <= j ? 1 : 0;
+  }
+  return R_m + g * level;
+}
+
+// A decode thread holds the columns col0 + i * STRIDE of its row in register i:
+// (lane, 64) in the narrow kernel, (tid, 512) in the wide one.
+//
+// The end of level g: r_g = acc - x goes to rrow, and the wave's sum of its
+// squares is returned (lane's registers ascending, then the xor tree).  At the
+// last level the registers keep r_g, which is S_{G-1}.
+template <int DL, int STRIDE>
+SPK_DEV float msp_level_close(float (&acc)[DL], const float* __restrict__ xrow,
+                              float* __restrict__ rrow, bool last, int d, int col0, int lane) {
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < DL; ++i) {
+    const int col = col0 + i * STRIDE;
+    float rv = 0.f;  // columns past d stay 0 for the dots of pass 1
+    if (col < d) {
+      rv = acc[i] - xrow[col];
+      rrow[col] = rv;
+    }
+    if (last) acc[i] = rv;
+    ss = __builtin_fmaf(rv, rv, ss);
+  }
+  return spk_wave_sum(ss, lane);
+}
+
+// On the way down: S += r_g, read back by the thread that wrote it, and S is
+// stored over it.
+template <int DL, int STRIDE>
+SPK_DEV void msp_level_down(float (&S)[DL], float* rrow, int d, int col0) {
+#pragma unroll
+  for (int i = 0; i < DL; ++i) {
+    const int col = col0 + i * STRIDE;
+    if (col < d) {
+      S[i] += rrow[col];
+      rrow[col] = S[i];
+    }
+  }
+}
 
 // ---------------------------------------------------------------------------
 // k_sparse_dec_gc: one wave owns one batch row of one model.
 // grid (ceil(B / 4), M); block SDG_T = 4 waves = 4 rows.
 //
-// Pass 0 scans the row of c in ascending column order.  Where the row's base is
-// 16-byte aligned, 256 columns go per step: a lane loads a float4, turns it
-// into a 4-bit mask, the wave ballots "any bit set" and walks the set lanes in
-// ascending order, and in each lane's mask the set bits in ascending order,
-// all of it wave-uniform (readlane).  The n % 4 tail, or the whole row where
-// the base is not aligned, goes 64 columns per step through a plain ballot.
-// Each hit j adds (c[b,j] inv[j]) * W[j,:] to the DL accumulators.  Then
-// r = acc - x is stored, and its squares are summed over the lane's registers,
-// the wave (xor tree), the block's four waves (LDS, pairwise), one atomicAdd
-// per block into loss_parts[m, 0], as k_dec_fwd_t does per wave.
-// Pass 1 scans the row again (it is in cache) with r still in the registers:
-// gpre[b,j] = (gscale inv[j]) * dot(r[b,:], W[j,:]), the dot summed over the
-// lane's registers and the wave's xor tree.  gpre is written at the hits only.
+// Pass 0 scans the row of c in ascending column order, level by level into the
+// SAME accumulators (a level's scan is sdg_scan on the segment [e_{g-1}, e_g),
+// its base pointers offset).  Where a segment's base is 16-byte aligned, 256
+// columns go per step: a lane loads a float4, turns it into a 4-bit mask, the
+// wave ballots "any bit set" and walks the set lanes in ascending order, and in
+// each lane's mask the set bits in ascending order, all of it wave-uniform
+// (readlane).  The n % 4 tail, or the whole segment where the base is not
+// aligned, goes 64 columns per step through a plain ballot.  Each hit j adds
+// (c[b,j] inv[j]) * W[j,:] to the DL accumulators.  The accumulator is never
+// reset, so at the boundary e_g it IS prefix g's reconstruction: r_g = acc - x
+// goes to R[m, g, b, :] (msp_level_close) and its squares are summed over the
+// lane's registers, the wave (xor tree), the block's four waves (LDS,
+// pairwise), one atomicAdd per level and block into parts[m * parts_stride + g],
+// as k_dec_fwd_t does per wave.  parts_stride is 2 for the plain loss_parts
+// and G for mse_parts.  A segment without a hit still gets its r_g and S.
+// Pass 1 goes down from g = G-1 with S in the same registers (acc is dead):
+// S = r_{G-1} as it stands, then msp_level_down, and segment g is scanned again
+// (it is in cache): gpre[b,j] = (gscale inv[j]) * dot(S_g[b,:], W[j,:]), the dot
+// summed over the lane's registers and the wave's xor tree.  gpre is written
+// at the hits only.
+//
+// Launch bounds.  The level loop and the boundary epilogue cost a few registers
+// over LEVELS = false; at DL = 16 that is more than 8 waves per SIMD leave (64:
+// the compiler spilled 32 bytes), so that instantiation asks for 4.
 // ---------------------------------------------------------------------------
 #define SDG_T 256
+
+constexpr int sdg_min_waves(int DL, bool LEVELS) {
+  return LEVELS ? (DL <= 12 ? 8 : DL <= 16 ? 4 : 2) : (DL <= 16 ? 8 : 2);
+}
 
 template <int DL, int PASS>
 SPK_DEV void sdg_hit(float (&acc)[DL], int j, float cv, const float* __restrict__ W,
@@ -1987,69 +2100,76 @@ SPK_DEV void sdg_scan(float (&acc)[DL], const float* __restrict__ crow, int n,
   }
 }
 
-template <int DL, int MINW>
+template <int DL, int MINW, bool LEVELS>
 __global__ __launch_bounds__(SDG_T, MINW) SPK_NOPK
 void k_sparse_dec_gc(const float* __restrict__ c,          // [M, B, n]
                      const float* __restrict__ Wdec,       // [M, n, d]
                      const float* __restrict__ inv_norms,  // [M, n]
                      const float* __restrict__ x,          // [B, d] or [M, B, d]
-                     float* __restrict__ r_out,            // [M, B, d]
+                     const int* __restrict__ ends,         // [M, G]; not read unless LEVELS
+                     float* R,                             // [M, G, B, d]: r_g, then S_g
                      float* __restrict__ gpre,             // [M, B, n], written at the hits only
-                     float* __restrict__ loss_parts,       // [M, 2]
-                     int B, int d, int n, long x_mstride) {
-  __shared__ float wave_ss[SDG_T / WAVE];
+                     float* __restrict__ parts,            // level g of model m at m * parts_stride + g
+                     int B, int d, int n, int levels, long x_mstride, int parts_stride) {
+  const int G = LEVELS ? levels : 1;
+  __shared__ float wave_ss[LEVELS ? MSP_MAX_G : 1][SDG_T / WAVE];
   const int lane = spk_tid() & (WAVE - 1);
   const int wave = spk_wave_id();
   const int m = (int)__builtin_amdgcn_workgroup_id_y();
   const int b = (int)__builtin_amdgcn_workgroup_id_x() * (SDG_T / WAVE) + wave;
+  const int* ends_m = ends + (long)m * G;
 
-  float ss = 0.f;
   if (b < B) {
     const float* crow = c + ((long)m * B + b) * n;
     const float* W = Wdec + (long)m * n * d;
     const float* inv = inv_norms + (long)m * n;
     const float* xrow = x + (long)m * x_mstride + (long)b * d;
-    float* rrow = r_out + ((long)m * B + b) * d;
+    float* Rrow = R + ((long)m * G * B + b) * d;  // level g's row: + g * level
+    const long level = (long)B * d;
     float* grow = gpre + ((long)m * B + b) * n;
     const float gscale = 2.0f / ((float)B * (float)d);
 
     float acc[DL];
 #pragma unroll
     for (int i = 0; i < DL; ++i) acc[i] = 0.f;
-    sdg_scan<DL, 0>(acc, crow, n, W, inv, grow, gscale, d, lane);
-#pragma unroll
-    for (int i = 0; i < DL; ++i) {
-      const int col = lane + i * WAVE;
-      float rv = 0.f;  // columns past d stay 0 for the dots of pass 1
-      if (col < d) {
-        rv = acc[i] - xrow[col];
-        rrow[col] = rv;
-      }
-      acc[i] = rv;
-      ss = __builtin_fmaf(rv, rv, ss);
+    int e0 = 0;
+    for (int g = 0; g < G; ++g) {
+      const int e1 = msp_end(ends_m, g, G, e0, n);
+      sdg_scan<DL, 0>(acc, crow + e0, e1 - e0, W + (long)e0 * d, inv + e0, grow + e0, gscale, d, lane);
+      const float ss = msp_level_close<DL, WAVE>(acc, xrow, Rrow + g * level, g == G - 1, d, lane, lane);
+      if (lane == 0) wave_ss[g][wave] = ss;
+      e0 = e1;
     }
-    ss = spk_wave_sum(ss, lane);
-    sdg_scan<DL, 1>(acc, crow, n, W, inv, grow, gscale, d, lane);
+    for (int g = G - 1; g >= 0; --g) {
+      int e1;
+      const int lo = msp_level_span(ends_m, g, G, n, e1);
+      if (g < G - 1) msp_level_down<DL, WAVE>(acc, Rrow + g * level, d, lane);
+      sdg_scan<DL, 1>(acc, crow + lo, e1 - lo, W + (long)lo * d, inv + lo, grow + lo, gscale, d, lane);
+    }
+  } else {
+    for (int g = lane; g < G; g += WAVE) wave_ss[g][wave] = 0.f;
   }
-  if (lane == 0) wave_ss[wave] = ss;
   spk_barrier();
-  if (spk_tid() == 0)
-    __hip_atomic_fetch_add(&loss_parts[m * 2 + 0],  // atomicAdd()
-                           (wave_ss[0] + wave_ss[1]) + (wave_ss[2] + wave_ss[3]),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (spk_tid() < G) {
+    const float* ws = wave_ss[spk_tid()];
+    __hip_atomic_fetch_add(&parts[(long)m * parts_stride + spk_tid()],  // atomicAdd()
+                           (ws[0] + ws[1]) + (ws[2] + ws[3]), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+  }
 }
 
 // ---------------------------------------------------------------------------
 // k_sparse_grad_w: one workgroup owns one model and a strip of 64 consecutive
 // features.  grid (ceil(n / 64), M); block SGW_T = 8 waves.
 //
-// Phase 1, hit lists.  The batch is cut into 8 contiguous row slices, one per
-// wave; thread (slice s, feature f) walks its rows in ascending order reading
-// c[b, j0 + f] (a wave reads 256 contiguous bytes per row).  A count pass, an
-// exclusive scan over the slices through LDS, and a fill pass leave, per
-// feature, the ascending list of its hit rows in hits[m, j, 0 .. count) and
-// the count in hit_counts[m, j].  The list's stride is B, its worst case: no
-// overflow.  Only the used prefix is ever written or read.
+// Phase 1, hit lists (sgw_hit_lists).  The batch is cut into 8 contiguous row
+// slices, one per wave; thread (slice s, feature f) walks its rows in ascending
+// order reading c[b, j0 + f] (a wave reads 256 contiguous bytes per row).  A
+// count pass, an exclusive scan over the slices through LDS, and a fill pass
+// leave, per feature, the ascending list of its hit rows in
+// hits[m, j, 0 .. count) and the count in hit_counts[m, j].  The list's stride
+// is B, its worst case: no overflow.  Only the used prefix is ever written or
+// read.
 //
 // The lists are consumed by the workgroup that built them, through global
 // memory: release fence, barrier, and a second fence behind the barrier, which
@@ -2057,21 +2177,25 @@ void k_sparse_dec_gc(const float* __restrict__ c,          // [M, B, n]
 // share with a neighbouring strip's (fetched by that strip's workgroup before
 // these writes landed).
 //
-// Phase 2, accumulate.  A feature with at most SGW_LIGHT hits is summed by one
-// wave alone, hits ascending (the features of the strip go round the waves).
-// A heavier feature's list is cut into 8 contiguous slices, one per wave, each
-// summed ascending; the 8 partials go through LDS and are added in ascending
-// slice order.  A feature that fires on every row thus costs B / 8 serial hits,
-// not B.  Which of the two a feature takes depends on its count alone, so the
-// result depends on nothing but the inputs.  Per hit: acc = fma(gscale c, r,
-// acc), then acc = fma(gpre, x, acc), two hits' loads in flight.  Every row of
-// gw is stored, +0 for a feature without a hit: gw needs no zeroing.
+// Phase 2, accumulate (sgw_strip_sums).  A feature with at most SGW_LIGHT hits
+// is summed by one wave alone, hits ascending (the features of the strip go
+// round the waves).  A heavier feature's list is cut into 8 contiguous slices,
+// one per wave, each summed ascending; the 8 partials go through LDS and are
+// added in ascending slice order.  A feature that fires on every row thus costs
+// B / 8 serial hits, not B.  Which of the two a feature takes depends on its
+// count alone, so the result depends on nothing but the inputs.  Per hit:
+// acc = fma(gscale c, S, acc), then acc = fma(gpre, x, acc), two hits' loads in
+// flight; S is the row of the feature's level of R (msp_level_rows).  Every row
+// of gw is stored, +0 for a feature without a hit: gw needs no zeroing.
 // ---------------------------------------------------------------------------
 #define SGW_T 512
 #define SGW_NW (SGW_T / WAVE)
 #define SGW_STRIP 64
 #define SGW_LIGHT 32
 #define SGW_CW_MAX 1024  // columns combined through LDS per round
+
+// columns of the LDS combine at depth DL
+constexpr int sgw_cw(int DL) { return DL * WAVE < SGW_CW_MAX ? DL * WAVE : SGW_CW_MAX; }
 
 template <int DL>
 struct SgwHit {
@@ -2131,363 +2255,129 @@ SPK_DEV void sgw_accum(float (&acc)[DL], const int* list, int lo, int hi,
   }
 }
 
-template <int DL, int MINW>
-__global__ __launch_bounds__(SGW_T, MINW) SPK_NOPK
-void k_sparse_grad_w(const float* __restrict__ c,     // [M, B, n]
-                     const float* __restrict__ gpre,  // [M, B, n], read at the hits only
-                     const float* __restrict__ r,     // [M, B, d]
-                     const float* __restrict__ x,     // [B, d] or [M, B, d]
-                     float* __restrict__ gw,          // [M, n, d]
-                     int* hits,                       // [M, n, B] ascending hit rows per feature
-                     int* __restrict__ hit_counts,    // [M, n]
-                     int B, int d, int n, long x_mstride) {
-  constexpr int CW = DL * WAVE < SGW_CW_MAX ? DL * WAVE : SGW_CW_MAX;
+// Phase 1 for the strip at j0: thread (slice = wave, feature = lane).  Leaves
+// the lists in hits_m [n, B] and the counts in counts_m [n], and returns the
+// total of the thread's feature.  Making the lists visible to their reader is
+// the caller's business.
+SPK_DEV int sgw_hit_lists(int j0, const float* c_m, int* hits_m,
+                          int* counts_m, int B, int n,
+                          SPK_LDS int (*cnt)[SGW_STRIP], int lane, int wave) {
+  const int j = j0 + lane;
+  const bool j_ok = j < n;
+  const int per = (B + SGW_NW - 1) / SGW_NW;
+  const int b_lo = spk_min(B, wave * per), b_hi = spk_min(B, b_lo + per);
+  const float* ccol = c_m + (j_ok ? j : 0);
+  int k = 0;
+  if (j_ok) {
+#pragma unroll 8
+    for (int b = b_lo; b < b_hi; ++b) k += ccol[(long)b * n] > 0.f ? 1 : 0;
+  }
+  cnt[wave][lane] = k;
+  spk_barrier();
+  int off = 0, total = 0;
+#pragma unroll
+  for (int s = 0; s < SGW_NW; ++s) {
+    const int v = cnt[s][lane];
+    if (s < wave) off += v;
+    total += v;
+  }
+  if (j_ok) {
+    int* list = hits_m + (long)j * B;
+#pragma unroll 8
+    for (int b = b_lo; b < b_hi; ++b)
+      if (ccol[(long)b * n] > 0.f) list[off++] = b;
+    if (wave == 0) counts_m[j] = total;
+  }
+  return total;
+}
+
+// Phase 2 for the strip at j0 over dw columns: every pointer to a row of
+// columns is already at the first of them, and ld is the row stride.  tot holds
+// the strip's counts; the heavy features' partials are combined through part in
+// DL * WAVE / sgw_cw(DL) rounds.
+template <int DL>
+SPK_DEV void sgw_strip_sums(const SPK_LDS int* tot, SPK_LDS float (*part)[sgw_cw(DL)], int j0,
+                            const int* hits_m, const float* c_m,
+                            const float* g_m, const float* R_m,
+                            const int* ends_m, const float* x_m,
+                            float* gw_m, int B, int n, int G, long level, float gscale,
+                            int ld, int dw, int lane, int wave) {
+  constexpr int CW = sgw_cw(DL);
   constexpr int NH = DL * WAVE / CW;  // combine rounds
   constexpr int RPH = CW / WAVE;      // registers per round
-  __shared__ int cnt[SGW_NW][SGW_STRIP];
-  __shared__ int tot[SGW_STRIP];
-  __shared__ float part[SGW_NW][CW];
 
-  const int lane = spk_tid() & (WAVE - 1);
-  const int wave = spk_wave_id();
-  const int m = (int)__builtin_amdgcn_workgroup_id_y();
-  const int j0 = (int)__builtin_amdgcn_workgroup_id_x() * SGW_STRIP;
-  const float* c_m = c + (long)m * B * n;
-  const float* g_m = gpre + (long)m * B * n;
-  const float* r_m = r + (long)m * B * d;
-  const float* x_m = x + (long)m * x_mstride;
-  float* gw_m = gw + (long)m * n * d;
-  const float gscale = 2.0f / ((float)B * (float)d);
-
-  // ---- phase 1: thread (slice = wave, feature = lane) ----------------------
-  {
-    const int j = j0 + lane;
-    const bool j_ok = j < n;
-    const int per = (B + SGW_NW - 1) / SGW_NW;
-    const int b_lo = spk_min(B, wave * per), b_hi = spk_min(B, b_lo + per);
-    const float* ccol = c_m + (j_ok ? j : 0);
-    int k = 0;
-    if (j_ok) {
-#pragma unroll 8
-      for (int b = b_lo; b < b_hi; ++b) k += ccol[(long)b * n] > 0.f ? 1 : 0;
-    }
-    cnt[wave][lane] = k;
-    spk_barrier();
-    int off = 0, total = 0;
-#pragma unroll
-    for (int s = 0; s < SGW_NW; ++s) {
-      const int v = cnt[s][lane];
-      if (s < wave) off += v;
-      total += v;
-    }
-    if (j_ok) {
-      int* list = hits + ((long)m * n + j) * B;
-#pragma unroll 8
-      for (int b = b_lo; b < b_hi; ++b)
-        if (ccol[(long)b * n] > 0.f) list[off++] = b;
-    }
-    if (wave == 0) {
-      tot[lane] = j_ok ? total : 0;
-      if (j_ok) hit_counts[(long)m * n + j] = total;
-    }
-    spk_fence_device();
-    spk_barrier();
-    spk_fence_device();
-  }
-
-  // ---- phase 2a: light features, one wave each ------------------------------
+  // ---- light features, one wave each ----------------------------------------
   float acc[DL];
   for (int f = wave; f < SGW_STRIP && j0 + f < n; f += SGW_NW) {
     const int j = j0 + f;
     const int count = tot[f];
     if (count > SGW_LIGHT) continue;
-    sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, 0, count, c_m + j, g_m + j, r_m, x_m,
-                  gscale, n, d, d, lane);
+    sgw_accum<DL>(acc, hits_m + (long)j * B, 0, count, c_m + j, g_m + j,
+                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, ld, dw, lane);
 #pragma unroll
     for (int i = 0; i < DL; ++i) {
       const int col = lane + i * WAVE;
-      if (col < d) gw_m[(long)j * d + col] = acc[i];
+      if (col < dw) gw_m[(long)j * ld + col] = acc[i];
     }
   }
 
-  // ---- phase 2b: heavy features, all waves each -----------------------------
+  // ---- heavy features, all waves each ---------------------------------------
   for (int f = 0; f < SGW_STRIP && j0 + f < n; ++f) {
     const int count = tot[f];
     if (count <= SGW_LIGHT) continue;  // block-uniform
     const int j = j0 + f;
     const int per = (count + SGW_NW - 1) / SGW_NW;
     const int lo = spk_min(count, wave * per), hi = spk_min(count, lo + per);
-    sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, lo, hi, c_m + j, g_m + j, r_m, x_m,
-                  gscale, n, d, d, lane);
+    sgw_accum<DL>(acc, hits_m + (long)j * B, lo, hi, c_m + j, g_m + j,
+                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, ld, dw, lane);
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
 #pragma unroll
       for (int ii = 0; ii < RPH; ++ii) part[wave][ii * WAVE + lane] = acc[h * RPH + ii];
       spk_barrier();
-      for (int col = spk_tid(); col < CW && h * CW + col < d; col += SGW_T) {
+      for (int col = spk_tid(); col < CW && h * CW + col < dw; col += SGW_T) {
         float s = part[0][col];
 #pragma unroll
         for (int w = 1; w < SGW_NW; ++w) s += part[w][col];
-        gw_m[(long)j * d + h * CW + col] = s;
+        gw_m[(long)j * ld + h * CW + col] = s;
       }
       spk_barrier();
     }
   }
 }
 
-// ---------------------------------------------------------------------------
-// Matryoshka BatchTopK (models/matryoshka.py): the features are cut into G <= 8
-// levels by the ascending ends e_0 < ... < e_{G-1} = n (`ends`, int32 [M, G]),
-// and the loss is the sum over g of mse(x, c[:, :e_g] @ What[:e_g]).  With
-// r_g = c[:, :e_g] @ What[:e_g] - x the residual of prefix g and
-// S_g = r_g + ... + r_{G-1}, a feature j of level g(j) has
-//   gpre[b,j] = (gscale inv[j]) dot(S_g(j)[b,:], W[j,:])
-//   gw[j,:]   = sum over its hit rows b of gscale c[b,j] S_g(j)[b,:] + gpre[b,j] x[b,:]
-// which is the plain chain with S_g(j) where that has r.  No level costs a GEMM:
-//
-//   k_msparse_dec_gc  k_sparse_dec_gc's wave per row.  Pass 0 scans the row
-//     level by level into the SAME accumulators (a level's scan is sdg_scan on
-//     the segment [e_{g-1}, e_g), its base pointers offset; a segment whose base
-//     is not 16-byte aligned takes the 64-wide ballot path).  The row is walked
-//     in ascending order and the accumulator is never reset, so at the boundary
-//     e_g it IS prefix g's reconstruction: r_g = acc - x goes to R[m, g, b, :]
-//     and its squares, summed as k_sparse_dec_gc sums them, to mse_parts[m, g]
-//     (one atomicAdd per level and block).  The last level's sum is the plain
-//     kernel's, bit for bit.  Pass 1 goes down from g = G-1 with S in the same
-//     registers (acc is dead): S = r_{G-1} as it stands, then S += r_g read back
-//     from R (the lane that wrote it reads it); S is stored over R[m, g, b, :]
-//     and segment g is rescanned for gpre at its hits.  A segment without a hit
-//     still gets its r_g and S.
-//   k_msparse_grad_w  k_sparse_grad_w's strip of 64 features, a feature's hits
-//     reading their residual rows from R[m, g(j)], which now holds S.  g(j)
-//     counts the ends <= j, wave-uniform; a strip may straddle a boundary.
-//
-// R costs 3 G B d floats of traffic per model (r_g out, back in, S out; the
-// last level is not rewritten).  Ends outside 0..n or out of order are clamped
-// into an ascending sequence: a bad `ends` gives wrong levels, never a wild
-// address.  The last level always ends at n.
-//
-// Registers and scratch, from the gfx950 code object's metadata as above.  The
-// level loop and the boundary epilogue cost k_msparse_dec_gc a few registers
-// over k_sparse_dec_gc; at DL = 16 that is more than 8 waves per SIMD leave
-// (64: the compiler spilled 32 bytes), so that depth asks for 4.  The waves
-// per SIMD below are what the launch bounds ask for and the VGPR counts allow
-// (512 / VGPRs): derived from the metadata, not observed on a device.
-//
-//   DL                       1    2    4    8   12   16   32
-//   k_msparse_dec_gc  VGPRs  26   24   27   38   52   71  182   (8 waves/SIMD asked for; 4 at DL = 16, 2 at DL = 32)
-//   k_msparse_grad_w  VGPRs  26   30   42   70  100  128  245   (4 waves/SIMD asked for; 2 at DL = 32)
-//   scratch bytes (both)     0    0    0    0    0    0    0
-// ---------------------------------------------------------------------------
-#define MSP_MAX_G 8
-
-// end of level g, clamped into [lo, n]; the last level ends at n
-SPK_DEV int msp_end(const int* __restrict__ ends_m, int g, int G, int lo, int n) {
-  if (g == G - 1) return n;
-  const int e = ends_m[g];
-  return e < lo ? lo : spk_min(e, n);
-}
-
-template <int DL, int MINW>
-__global__ __launch_bounds__(SDG_T, MINW) SPK_NOPK
-void k_msparse_dec_gc(const float* __restrict__ c,          // [M, B, n]
-                      const float* __restrict__ Wdec,       // [M, n, d]
-                      const float* __restrict__ inv_norms,  // [M, n]
-                      const float* __restrict__ x,          // [B, d] or [M, B, d]
-                      const int* __restrict__ ends,         // [M, G]
-                      float* R,                             // [M, G, B, d]: r_g, then S_g
-                      float* __restrict__ gpre,             // [M, B, n], written at the hits only
-                      float* __restrict__ mse_parts,        // [M, G]
-                      int B, int d, int n, int G, long x_mstride) {
-  __shared__ float wave_ss[MSP_MAX_G][SDG_T / WAVE];
-  const int lane = spk_tid() & (WAVE - 1);
-  const int wave = spk_wave_id();
-  const int m = (int)__builtin_amdgcn_workgroup_id_y();
-  const int b = (int)__builtin_amdgcn_workgroup_id_x() * (SDG_T / WAVE) + wave;
-  const int* ends_m = ends + (long)m * G;
-
-  if (b < B) {
-    const float* crow = c + ((long)m * B + b) * n;
-    const float* W = Wdec + (long)m * n * d;
-    const float* inv = inv_norms + (long)m * n;
-    const float* xrow = x + (long)m * x_mstride + (long)b * d;
-    float* Rrow = R + ((long)m * G * B + b) * d;  // level g's row: + g * level
-    const long level = (long)B * d;
-    float* grow = gpre + ((long)m * B + b) * n;
-    const float gscale = 2.0f / ((float)B * (float)d);
-
-    float acc[DL];
-#pragma unroll
-    for (int i = 0; i < DL; ++i) acc[i] = 0.f;
-    int e0 = 0;
-    for (int g = 0; g < G; ++g) {
-      const int e1 = msp_end(ends_m, g, G, e0, n);
-      sdg_scan<DL, 0>(acc, crow + e0, e1 - e0, W + (long)e0 * d, inv + e0, grow + e0, gscale, d, lane);
-      float* rrow = Rrow + g * level;
-      const bool last = g == G - 1;
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < DL; ++i) {
-        const int col = lane + i * WAVE;
-        float rv = 0.f;  // columns past d stay 0 for the dots of pass 1
-        if (col < d) {
-          rv = acc[i] - xrow[col];
-          rrow[col] = rv;
-        }
-        if (last) acc[i] = rv;  // S_{G-1} = r_{G-1}
-        ss = __builtin_fmaf(rv, rv, ss);
-      }
-      ss = spk_wave_sum(ss, lane);
-      if (lane == 0) wave_ss[g][wave] = ss;
-      e0 = e1;
-    }
-    for (int g = G - 1; g >= 0; --g) {
-      // the clamped ends again, from the top: e1 of level g is e0 of level g + 1
-      int lo = 0;
-      for (int h = 0; h < g; ++h) lo = msp_end(ends_m, h, G, lo, n);
-      const int e1 = msp_end(ends_m, g, G, lo, n);
-      if (g < G - 1) {
-        float* rrow = Rrow + g * level;
-#pragma unroll
-        for (int i = 0; i < DL; ++i) {
-          const int col = lane + i * WAVE;
-          if (col < d) {
-            acc[i] += rrow[col];
-            rrow[col] = acc[i];
-          }
-        }
-      }
-      sdg_scan<DL, 1>(acc, crow + lo, e1 - lo, W + (long)lo * d, inv + lo, grow + lo, gscale, d, lane);
-    }
-  } else {
-    for (int g = lane; g < G; g += WAVE) wave_ss[g][wave] = 0.f;
-  }
-  spk_barrier();
-  if (spk_tid() < G) {
-    const float* ws = wave_ss[spk_tid()];
-    __hip_atomic_fetch_add(&mse_parts[m * G + spk_tid()], (ws[0] + ws[1]) + (ws[2] + ws[3]),
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// R[m, g(j)]: the [B, d] block feature j's hits read their residual rows from
-SPK_DEV const float* msp_level_rows(const float* __restrict__ R_m, const int* __restrict__ ends_m,
-                                    int j, int G, int n, long level) {
-  int g = 0, lo = 0;
-  for (int h = 0; h < G - 1; ++h) {
-    lo = msp_end(ends_m, h, G, lo, n);
-    g += lo <= j ? 1 : 0;
-  }
-  return R_m + g * level;
-}
-
-// k_sparse_grad_w's phases, statement for statement (that kernel's code object
-// is pinned, so the body is repeated here and not shared): the two
-// sgw_accum calls take a feature's own level of R.
-template <int DL, int MINW>
+template <int DL, int MINW, bool LEVELS>
 __global__ __launch_bounds__(SGW_T, MINW) SPK_NOPK
-void k_msparse_grad_w(const float* __restrict__ c,     // [M, B, n]
-                      const float* __restrict__ gpre,  // [M, B, n], read at the hits only
-                      const float* __restrict__ R,     // [M, G, B, d]: S_g
-                      const float* __restrict__ x,     // [B, d] or [M, B, d]
-                      const int* __restrict__ ends,    // [M, G]
-                      float* __restrict__ gw,          // [M, n, d]
-                      int* hits,                       // [M, n, B] ascending hit rows per feature
-                      int* __restrict__ hit_counts,    // [M, n]
-                      int B, int d, int n, int G, long x_mstride) {
-  constexpr int CW = DL * WAVE < SGW_CW_MAX ? DL * WAVE : SGW_CW_MAX;
-  constexpr int NH = DL * WAVE / CW;  // combine rounds
-  constexpr int RPH = CW / WAVE;      // registers per round
+void k_sparse_grad_w(const float* __restrict__ c,     // [M, B, n]
+                     const float* __restrict__ gpre,  // [M, B, n], read at the hits only
+                     const float* __restrict__ R,     // [M, G, B, d]: S_g
+                     const float* __restrict__ x,     // [B, d] or [M, B, d]
+                     const int* __restrict__ ends,    // [M, G]; not read unless LEVELS
+                     float* __restrict__ gw,          // [M, n, d]
+                     int* hits,                       // [M, n, B] ascending hit rows per feature
+                     int* __restrict__ hit_counts,    // [M, n]
+                     int B, int d, int n, int levels, long x_mstride) {
+  const int G = LEVELS ? levels : 1;
   __shared__ int cnt[SGW_NW][SGW_STRIP];
   __shared__ int tot[SGW_STRIP];
-  __shared__ float part[SGW_NW][CW];
+  __shared__ float part[SGW_NW][sgw_cw(DL)];
 
   const int lane = spk_tid() & (WAVE - 1);
   const int wave = spk_wave_id();
   const int m = (int)__builtin_amdgcn_workgroup_id_y();
   const int j0 = (int)__builtin_amdgcn_workgroup_id_x() * SGW_STRIP;
   const long level = (long)B * d;
-  const float* c_m = c + (long)m * B * n;
-  const float* g_m = gpre + (long)m * B * n;
-  const float* R_m = R + (long)m * G * level;
-  const int* ends_m = ends + (long)m * G;
-  const float* x_m = x + (long)m * x_mstride;
-  float* gw_m = gw + (long)m * n * d;
-  const float gscale = 2.0f / ((float)B * (float)d);
+  int* hits_m = hits + (long)m * n * B;
 
-  // ---- phase 1: thread (slice = wave, feature = lane) ----------------------
-  {
-    const int j = j0 + lane;
-    const bool j_ok = j < n;
-    const int per = (B + SGW_NW - 1) / SGW_NW;
-    const int b_lo = spk_min(B, wave * per), b_hi = spk_min(B, b_lo + per);
-    const float* ccol = c_m + (j_ok ? j : 0);
-    int k = 0;
-    if (j_ok) {
-#pragma unroll 8
-      for (int b = b_lo; b < b_hi; ++b) k += ccol[(long)b * n] > 0.f ? 1 : 0;
-    }
-    cnt[wave][lane] = k;
-    spk_barrier();
-    int off = 0, total = 0;
-#pragma unroll
-    for (int s = 0; s < SGW_NW; ++s) {
-      const int v = cnt[s][lane];
-      if (s < wave) off += v;
-      total += v;
-    }
-    if (j_ok) {
-      int* list = hits + ((long)m * n + j) * B;
-#pragma unroll 8
-      for (int b = b_lo; b < b_hi; ++b)
-        if (ccol[(long)b * n] > 0.f) list[off++] = b;
-    }
-    if (wave == 0) {
-      tot[lane] = j_ok ? total : 0;
-      if (j_ok) hit_counts[(long)m * n + j] = total;
-    }
-    spk_fence_device();
-    spk_barrier();
-    spk_fence_device();
-  }
+  const int total = sgw_hit_lists(j0, c + (long)m * B * n, hits_m, hit_counts + (long)m * n, B, n,
+                                  spk_lds(cnt), lane, wave);
+  if (wave == 0) tot[lane] = total;
+  spk_fence_device();
+  spk_barrier();
+  spk_fence_device();
 
-  // ---- phase 2a: light features, one wave each ------------------------------
-  float acc[DL];
-  for (int f = wave; f < SGW_STRIP && j0 + f < n; f += SGW_NW) {
-    const int j = j0 + f;
-    const int count = tot[f];
-    if (count > SGW_LIGHT) continue;
-    sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, 0, count, c_m + j, g_m + j,
-                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, d, d, lane);
-#pragma unroll
-    for (int i = 0; i < DL; ++i) {
-      const int col = lane + i * WAVE;
-      if (col < d) gw_m[(long)j * d + col] = acc[i];
-    }
-  }
-
-  // ---- phase 2b: heavy features, all waves each -----------------------------
-  for (int f = 0; f < SGW_STRIP && j0 + f < n; ++f) {
-    const int count = tot[f];
-    if (count <= SGW_LIGHT) continue;  // block-uniform
-    const int j = j0 + f;
-    const int per = (count + SGW_NW - 1) / SGW_NW;
-    const int lo = spk_min(count, wave * per), hi = spk_min(count, lo + per);
-    sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, lo, hi, c_m + j, g_m + j,
-                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, d, d, lane);
-#pragma unroll
-    for (int h = 0; h < NH; ++h) {
-#pragma unroll
-      for (int ii = 0; ii < RPH; ++ii) part[wave][ii * WAVE + lane] = acc[h * RPH + ii];
-      spk_barrier();
-      for (int col = spk_tid(); col < CW && h * CW + col < d; col += SGW_T) {
-        float s = part[0][col];
-#pragma unroll
-        for (int w = 1; w < SGW_NW; ++w) s += part[w][col];
-        gw_m[(long)j * d + h * CW + col] = s;
-      }
-      spk_barrier();
-    }
-  }
+  sgw_strip_sums<DL>(spk_lds(tot), spk_lds(part), j0, hits_m, c + (long)m * B * n, gpre + (long)m * B * n,
+                     R + (long)m * G * level, ends + (long)m * G, x + (long)m * x_mstride,
+                     gw + (long)m * n * d, B, n, G, level, 2.0f / ((float)B * (float)d), d, d, lane,
+                     wave);
 }
-

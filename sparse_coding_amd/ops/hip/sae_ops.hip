@@ -476,34 +476,80 @@ static SparseShape sparse_shape(const char* who, const torch::Tensor& c, const t
   return {(int)M, (int)B, (int)n, (int)d, x_model_stride(x, (int)M)};
 }
 
-// The wide decode (d > SPARSE_MAX_D) of both chains: the plain one is G = 1
-// with R = r and its loss at stride 2.
-static void wsparse_dec_gc_launch(const SparseShape& s, const torch::Tensor& c, const torch::Tensor& W,
-                                  const torch::Tensor& inv_norms, const torch::Tensor& x,
-                                  const int* ends_p, int G, torch::Tensor& R, torch::Tensor& gpre,
-                                  torch::Tensor& parts, int parts_stride) {
-  dim3 grid(s.B, s.M);
-#define LAUNCH_WSDG(DLW)                                                                      \
-  hipLaunchKernelGGL((k_wsparse_dec_gc<DLW, 4>), grid, dim3(WSP_T), 0, cur_stream(),          \
-                     c.data_ptr<float>(), W.data_ptr<float>(), inv_norms.data_ptr<float>(),   \
-                     x.data_ptr<float>(), ends_p, R.data_ptr<float>(), gpre.data_ptr<float>(), \
+// The decode of both chains, narrow and wide.  The plain chain comes with
+// ends_p = nullptr, G = 1, R = r and its loss at stride 2; the Matryoshka chain
+// with its ends, R [M, G, B, d] and mse_parts at stride G.
+static void sparse_dec_gc_launch(const char* who, const SparseShape& s, const torch::Tensor& c,
+                                 const torch::Tensor& W, const torch::Tensor& inv_norms,
+                                 const torch::Tensor& x, const int* ends_p, int G, torch::Tensor& R,
+                                 torch::Tensor& gpre, torch::Tensor& parts, int parts_stride) {
+  TORCH_CHECK(W.dim() == 3 && W.size(0) == s.M && W.size(1) == s.n && W.size(2) == s.d,
+              who, ": W must be [M,n,d]");
+  TORCH_CHECK(inv_norms.numel() == (long)s.M * s.n, who, ": inv_norms must be [M,n]");
+  if (s.M == 0 || s.B == 0) return;
+#define LAUNCH_DEC_GC(KERNEL, T, grid)                                                        \
+  hipLaunchKernelGGL(KERNEL, grid, dim3(T), 0, cur_stream(), c.data_ptr<float>(),             \
+                     W.data_ptr<float>(), inv_norms.data_ptr<float>(), x.data_ptr<float>(),   \
+                     ends_p, R.data_ptr<float>(), gpre.data_ptr<float>(),                     \
                      parts.data_ptr<float>(), s.B, s.d, s.n, G, s.x_mstride, parts_stride)
-  if (s.d <= 8 * WSP_T) LAUNCH_WSDG(8);
-  else LAUNCH_WSDG(16);
-#undef LAUNCH_WSDG
+  if (s.d > SPARSE_MAX_D) {
+    if (s.d <= 8 * WSP_T) LAUNCH_DEC_GC((k_wsparse_dec_gc<8, 4>), WSP_T, dim3(s.B, s.M));
+    else LAUNCH_DEC_GC((k_wsparse_dec_gc<16, 4>), WSP_T, dim3(s.B, s.M));
+    return;
+  }
+#define LAUNCH_SDG_AS(DL, LEVELS)                                                             \
+  LAUNCH_DEC_GC((k_sparse_dec_gc<DL, sdg_min_waves(DL, LEVELS), LEVELS>), SDG_T,              \
+                dim3(cdiv(s.B, SDG_T / WAVE), s.M))
+#define LAUNCH_SDG(DL)                                                                        \
+  do {                                                                                        \
+    if (ends_p) LAUNCH_SDG_AS(DL, true);                                                      \
+    else LAUNCH_SDG_AS(DL, false);                                                            \
+  } while (0)
+  SPARSE_DISPATCH_DL(s.d, LAUNCH_SDG);
+#undef LAUNCH_SDG
+#undef LAUNCH_SDG_AS
+#undef LAUNCH_DEC_GC
 }
 
-// The wide weight gradient of both chains: the hit lists in a launch of their
-// own, then one workgroup per strip of 64 features and window of 1024 columns.
-static void wsparse_grad_w_launch(const SparseShape& s, const torch::Tensor& c, const torch::Tensor& gpre,
-                                  const torch::Tensor& R, const torch::Tensor& x, const int* ends_p,
-                                  int G, torch::Tensor& gw, int* hits_p, int* counts_p) {
-  hipLaunchKernelGGL(k_sparse_hit_lists, dim3(cdiv(s.n, SGW_STRIP), s.M), dim3(SGW_T), 0,
-                     cur_stream(), c.data_ptr<float>(), hits_p, counts_p, s.B, s.n);
-  hipLaunchKernelGGL(k_wsparse_grad_w, dim3(cdiv(s.n, SGW_STRIP), cdiv(s.d, WSGW_CHUNK), s.M),
-                     dim3(SGW_T), 0, cur_stream(), c.data_ptr<float>(), gpre.data_ptr<float>(),
-                     R.data_ptr<float>(), x.data_ptr<float>(), ends_p, gw.data_ptr<float>(),
-                     (const int*)hits_p, (const int*)counts_p, s.B, s.d, s.n, G, s.x_mstride);
+// The weight gradient of both chains, with the same convention for ends_p, G
+// and R.  Narrow: one launch, minimum waves per SIMD by depth.  Wide: the hit
+// lists in a launch of their own, then one workgroup per strip of 64 features
+// and window of 1024 columns.
+static void sparse_grad_w_launch(const char* who, const SparseShape& s, const torch::Tensor& c,
+                                 const torch::Tensor& gpre, const torch::Tensor& R,
+                                 const torch::Tensor& x, const int* ends_p, int G, torch::Tensor& gw,
+                                 const torch::Tensor& hits, const torch::Tensor& hit_counts) {
+  TORCH_CHECK(gw.dim() == 3 && gw.size(0) == s.M && gw.size(1) == s.n && gw.size(2) == s.d,
+              who, ": gw must be [M,n,d]");
+  TORCH_CHECK(hits.numel() >= sparse_hits_size(s.M, s.B, s.n),
+              who, ": hits needs sparse_hits_size(M, B, n) int32 elements");
+  TORCH_CHECK(hit_counts.numel() == (long)s.M * s.n, who, ": hit_counts must be [M,n]");
+  int* hits_p = int32_ptr(hits, "hits");
+  int* counts_p = int32_ptr(hit_counts, "hit_counts");
+  if (s.M == 0 || s.n == 0) return;
+#define LAUNCH_GRAD_W(KERNEL, grid, hits_arg, counts_arg)                                     \
+  hipLaunchKernelGGL(KERNEL, grid, dim3(SGW_T), 0, cur_stream(), c.data_ptr<float>(),         \
+                     gpre.data_ptr<float>(), R.data_ptr<float>(), x.data_ptr<float>(), ends_p, \
+                     gw.data_ptr<float>(), hits_arg, counts_arg, s.B, s.d, s.n, G, s.x_mstride)
+  if (s.d > SPARSE_MAX_D) {
+    hipLaunchKernelGGL(k_sparse_hit_lists, dim3(cdiv(s.n, SGW_STRIP), s.M), dim3(SGW_T), 0,
+                       cur_stream(), c.data_ptr<float>(), hits_p, counts_p, s.B, s.n);
+    LAUNCH_GRAD_W(k_wsparse_grad_w, dim3(cdiv(s.n, SGW_STRIP), cdiv(s.d, WSGW_CHUNK), s.M),
+                  (const int*)hits_p, (const int*)counts_p);
+    return;
+  }
+#define LAUNCH_SGW_AS(DL, LEVELS)                                                             \
+  LAUNCH_GRAD_W((k_sparse_grad_w<DL, (DL <= 16 ? 4 : 2), LEVELS>),                            \
+                dim3(cdiv(s.n, SGW_STRIP), s.M), hits_p, counts_p)
+#define LAUNCH_SGW(DL)                                                                        \
+  do {                                                                                        \
+    if (ends_p) LAUNCH_SGW_AS(DL, true);                                                      \
+    else LAUNCH_SGW_AS(DL, false);                                                            \
+  } while (0)
+  SPARSE_DISPATCH_DL(s.d, LAUNCH_SGW);
+#undef LAUNCH_SGW
+#undef LAUNCH_SGW_AS
+#undef LAUNCH_GRAD_W
 }
 
 void sparse_dec_gc(torch::Tensor c, torch::Tensor W, torch::Tensor inv_norms, torch::Tensor x,
@@ -511,52 +557,21 @@ void sparse_dec_gc(torch::Tensor c, torch::Tensor W, torch::Tensor inv_norms, to
   CHECK_IN(c); CHECK_IN(W); CHECK_IN(inv_norms); CHECK_IN(x); CHECK_IN(r); CHECK_IN(gpre);
   CHECK_IN(loss_parts);
   const SparseShape s = sparse_shape("sparse_dec_gc", c, gpre, r, x);
-  TORCH_CHECK(W.dim() == 3 && W.size(0) == s.M && W.size(1) == s.n && W.size(2) == s.d,
-              "sparse_dec_gc: W must be [M,n,d]");
-  TORCH_CHECK(inv_norms.numel() == (long)s.M * s.n, "sparse_dec_gc: inv_norms must be [M,n]");
   TORCH_CHECK(loss_parts.numel() == (long)s.M * 2, "sparse_dec_gc: loss_parts must be [M,2]");
-  if (s.M == 0 || s.B == 0) return;
-  if (s.d > SPARSE_MAX_D)
-    return wsparse_dec_gc_launch(s, c, W, inv_norms, x, nullptr, 1, r, gpre, loss_parts, 2);
-  dim3 grid(cdiv(s.B, SDG_T / WAVE), s.M);
-#define LAUNCH_SDG(DL)                                                                        \
-  hipLaunchKernelGGL((k_sparse_dec_gc<DL, (DL <= 16 ? 8 : 2)>), grid, dim3(SDG_T), 0,         \
-                     cur_stream(), c.data_ptr<float>(), W.data_ptr<float>(),                  \
-                     inv_norms.data_ptr<float>(), x.data_ptr<float>(), r.data_ptr<float>(),   \
-                     gpre.data_ptr<float>(), loss_parts.data_ptr<float>(), s.B, s.d, s.n,     \
-                     s.x_mstride)
-  SPARSE_DISPATCH_DL(s.d, LAUNCH_SDG);
-#undef LAUNCH_SDG
+  sparse_dec_gc_launch("sparse_dec_gc", s, c, W, inv_norms, x, nullptr, 1, r, gpre, loss_parts, 2);
 }
 
 void sparse_grad_w(torch::Tensor c, torch::Tensor gpre, torch::Tensor r, torch::Tensor x,
                    torch::Tensor gw, torch::Tensor hits, torch::Tensor hit_counts) {
   CHECK_IN(c); CHECK_IN(gpre); CHECK_IN(r); CHECK_IN(x); CHECK_IN(gw);
   const SparseShape s = sparse_shape("sparse_grad_w", c, gpre, r, x);
-  TORCH_CHECK(gw.dim() == 3 && gw.size(0) == s.M && gw.size(1) == s.n && gw.size(2) == s.d,
-              "sparse_grad_w: gw must be [M,n,d]");
-  TORCH_CHECK(hits.numel() >= sparse_hits_size(s.M, s.B, s.n),
-              "sparse_grad_w: hits needs sparse_hits_size(M, B, n) int32 elements");
-  TORCH_CHECK(hit_counts.numel() == (long)s.M * s.n, "sparse_grad_w: hit_counts must be [M,n]");
-  int* hits_p = int32_ptr(hits, "hits");
-  int* counts_p = int32_ptr(hit_counts, "hit_counts");
-  if (s.M == 0 || s.n == 0) return;
-  if (s.d > SPARSE_MAX_D)
-    return wsparse_grad_w_launch(s, c, gpre, r, x, nullptr, 1, gw, hits_p, counts_p);
-  dim3 grid(cdiv(s.n, SGW_STRIP), s.M);
-#define LAUNCH_SGW(DL)                                                                        \
-  hipLaunchKernelGGL((k_sparse_grad_w<DL, (DL <= 16 ? 4 : 2)>), grid, dim3(SGW_T), 0,         \
-                     cur_stream(), c.data_ptr<float>(), gpre.data_ptr<float>(),               \
-                     r.data_ptr<float>(), x.data_ptr<float>(), gw.data_ptr<float>(), hits_p,  \
-                     counts_p, s.B, s.d, s.n, s.x_mstride)
-  SPARSE_DISPATCH_DL(s.d, LAUNCH_SGW);
-#undef LAUNCH_SGW
+  sparse_grad_w_launch("sparse_grad_w", s, c, gpre, r, x, nullptr, 1, gw, hits, hit_counts);
 }
 
-// The Matryoshka chain (k_msparse_dec_gc / k_msparse_grad_w): the sparse chain
-// with G nested levels.  ends is int32 [M, G], R is [M, G, B, d] (r_g out of
-// the decode's first pass, S_g = r_g + ... + r_{G-1} when it returns) and
-// mse_parts [M, G] is accumulated into, as loss_parts is.
+// The Matryoshka chain: the sparse chain with G nested levels.  ends is int32
+// [M, G], R is [M, G, B, d] (r_g out of the decode's first pass,
+// S_g = r_g + ... + r_{G-1} when it returns) and mse_parts [M, G] is
+// accumulated into, as loss_parts is.
 static int msparse_levels(const char* who, const SparseShape& s, const torch::Tensor& ends,
                           const torch::Tensor& R) {
   TORCH_CHECK(ends.dim() == 2 && ends.size(0) == s.M, who, ": ends must be int32 [M,G]");
@@ -574,25 +589,10 @@ void msparse_dec_gc(torch::Tensor c, torch::Tensor W, torch::Tensor inv_norms, t
   TORCH_CHECK(R.dim() == 4, "msparse_dec_gc: R must be [M,G,B,d]");
   const SparseShape s = sparse_shape("msparse_dec_gc", c, gpre, R.select(1, 0), x);
   const int G = msparse_levels("msparse_dec_gc", s, ends, R);
-  TORCH_CHECK(W.dim() == 3 && W.size(0) == s.M && W.size(1) == s.n && W.size(2) == s.d,
-              "msparse_dec_gc: W must be [M,n,d]");
-  TORCH_CHECK(inv_norms.numel() == (long)s.M * s.n, "msparse_dec_gc: inv_norms must be [M,n]");
   TORCH_CHECK(mse_parts.dim() == 2 && mse_parts.size(0) == s.M && mse_parts.size(1) == G,
               "msparse_dec_gc: mse_parts must be [M,G]");
-  const int* ends_p = int32_ptr(ends, "ends");
-  if (s.M == 0 || s.B == 0) return;
-  if (s.d > SPARSE_MAX_D)
-    return wsparse_dec_gc_launch(s, c, W, inv_norms, x, ends_p, G, R, gpre, mse_parts, G);
-  dim3 grid(cdiv(s.B, SDG_T / WAVE), s.M);
-#define LAUNCH_MSDG(DL)                                                                       \
-  hipLaunchKernelGGL((k_msparse_dec_gc<DL, (DL <= 12 ? 8 : DL <= 16 ? 4 : 2)>), grid,         \
-                     dim3(SDG_T), 0,                                                          \
-                     cur_stream(), c.data_ptr<float>(), W.data_ptr<float>(),                  \
-                     inv_norms.data_ptr<float>(), x.data_ptr<float>(), ends_p,                \
-                     R.data_ptr<float>(), gpre.data_ptr<float>(), mse_parts.data_ptr<float>(), \
-                     s.B, s.d, s.n, G, s.x_mstride)
-  SPARSE_DISPATCH_DL(s.d, LAUNCH_MSDG);
-#undef LAUNCH_MSDG
+  sparse_dec_gc_launch("msparse_dec_gc", s, c, W, inv_norms, x, int32_ptr(ends, "ends"), G, R, gpre,
+                       mse_parts, G);
 }
 
 void msparse_grad_w(torch::Tensor c, torch::Tensor gpre, torch::Tensor R, torch::Tensor x,
@@ -601,25 +601,8 @@ void msparse_grad_w(torch::Tensor c, torch::Tensor gpre, torch::Tensor R, torch:
   TORCH_CHECK(R.dim() == 4, "msparse_grad_w: R must be [M,G,B,d]");
   const SparseShape s = sparse_shape("msparse_grad_w", c, gpre, R.select(1, 0), x);
   const int G = msparse_levels("msparse_grad_w", s, ends, R);
-  TORCH_CHECK(gw.dim() == 3 && gw.size(0) == s.M && gw.size(1) == s.n && gw.size(2) == s.d,
-              "msparse_grad_w: gw must be [M,n,d]");
-  TORCH_CHECK(hits.numel() >= sparse_hits_size(s.M, s.B, s.n),
-              "msparse_grad_w: hits needs sparse_hits_size(M, B, n) int32 elements");
-  TORCH_CHECK(hit_counts.numel() == (long)s.M * s.n, "msparse_grad_w: hit_counts must be [M,n]");
-  const int* ends_p = int32_ptr(ends, "ends");
-  int* hits_p = int32_ptr(hits, "hits");
-  int* counts_p = int32_ptr(hit_counts, "hit_counts");
-  if (s.M == 0 || s.n == 0) return;
-  if (s.d > SPARSE_MAX_D)
-    return wsparse_grad_w_launch(s, c, gpre, R, x, ends_p, G, gw, hits_p, counts_p);
-  dim3 grid(cdiv(s.n, SGW_STRIP), s.M);
-#define LAUNCH_MSGW(DL)                                                                       \
-  hipLaunchKernelGGL((k_msparse_grad_w<DL, (DL <= 16 ? 4 : 2)>), grid, dim3(SGW_T), 0,        \
-                     cur_stream(), c.data_ptr<float>(), gpre.data_ptr<float>(),               \
-                     R.data_ptr<float>(), x.data_ptr<float>(), ends_p, gw.data_ptr<float>(),  \
-                     hits_p, counts_p, s.B, s.d, s.n, G, s.x_mstride)
-  SPARSE_DISPATCH_DL(s.d, LAUNCH_MSGW);
-#undef LAUNCH_MSGW
+  sparse_grad_w_launch("msparse_grad_w", s, c, gpre, R, x, int32_ptr(ends, "ends"), G, gw, hits,
+                       hit_counts);
 }
 
 // The AuxK chain of the TopK step (sae_auxk.hip).  Per model: ages [n] int32,

@@ -14,8 +14,8 @@
 //   k_wsparse_grad_w    k_sparse_grad_w's phase 2 per window of 1024 columns,
 //                       reading those lists
 //
-// All three are level-aware (G nested prefixes, as the k_msparse_* kernels);
-// the plain chain is G = 1 with R = r.  A column's sums run in the order of the
+// All three are level-aware (G nested prefixes, as the narrow kernels' LEVELS
+// instantiations); the plain chain is G = 1 with R = r.  A column's sums run in the order of the
 // narrow kernels (ascending features for r, ascending hit rows for gw, the same
 // light/heavy rule), so a column of r or gw holds the bits a narrow launch on
 // that column gives.  Only gpre's dot and the loss are reduced differently:
@@ -31,7 +31,7 @@
 //   k_wsparse_dec_gc   DLW = 8    67      0      33120     4 asked for; 6 (three workgroups; LDS lets four in)
 //   k_wsparse_dec_gc   DLW = 16  124      0      33120     4 asked for; 4
 //   k_sparse_hit_lists            25      0       2048     8
-//   k_wsparse_grad_w   DL = 16   128      0      33024     2 asked for (see the kernel); 4
+//   k_wsparse_grad_w   DL = 16   122      0      33024     2 asked for (see the kernel); 4
 
 #define WSP_T 512              // 8 waves: wave w, register i, lane l own column (i * 8 + w) * 64 + l
 #define WSP_NW (WSP_T / WAVE)
@@ -213,10 +213,9 @@ SPK_DEV void wsp_gpre(const float (&S)[DLW], WspLds& L, int lo, int hi, const fl
 // Pass 0 fills the list from the row (wsp_fill) and walks it; at a level's end
 // e_g the walk stops at the first entry with j >= e_g, r_g = acc - x goes to
 // R[m, g, b, :] and its squares to the level's sum, and the walk goes on into
-// the SAME accumulators, as k_msparse_dec_gc's does.  A row with more than
+// the SAME accumulators, as k_sparse_dec_gc's does.  A row with more than
 // WSP_CAP hits fills, consumes and refills the list; nothing assumes k.
-// Pass 1 goes down from g = G-1 with S_g in the registers (S += r_g read back
-// by the thread that wrote it, S stored over it).  Where the row fitted one
+// Pass 1 goes down from g = G-1 with S_g in the registers (msp_level_down).  Where the row fitted one
 // fill, the normal case, the list is still whole and level g's entries are
 // [level_hi[g-1], level_hi[g]): c is not read again.  Otherwise level g's
 // columns are rescanned, fill by fill.
@@ -266,21 +265,8 @@ void k_wsparse_dec_gc(const float* __restrict__ c,          // [M, B, n]
       wsp_walk<DLW>(acc, L, h, hi, W, d, col0);
       h = hi;
       if (h == count && !done) break;  // level g may go on in the next fill
-      float* rrow = Rrow + g * level;
-      const bool last = g == G - 1;
-      float ss = 0.f;
-#pragma unroll
-      for (int i = 0; i < DLW; ++i) {
-        const int col = col0 + i * WSP_T;
-        float rv = 0.f;  // columns past d stay 0 for the dots of pass 1
-        if (col < d) {
-          rv = acc[i] - xrow[col];
-          rrow[col] = rv;
-        }
-        if (last) acc[i] = rv;  // S_{G-1} = r_{G-1}
-        ss = __builtin_fmaf(rv, rv, ss);
-      }
-      ss = spk_wave_sum(ss, lane);
+      const float ss =
+          msp_level_close<DLW, WSP_T>(acc, xrow, Rrow + g * level, g == G - 1, d, col0, lane);
       if (lane == 0) L.wave_ss[g][wave] = ss;
       if (spk_tid() == 0) L.level_hi[g] = h;
       ++g;
@@ -290,21 +276,8 @@ void k_wsparse_dec_gc(const float* __restrict__ c,          // [M, B, n]
   spk_barrier();  // level_hi
 
   for (g = G - 1; g >= 0; --g) {
-    // the clamped ends again, from the top: e1 of level g is e0 of level g + 1
-    int lo = 0;
-    for (int h = 0; h < g; ++h) lo = msp_end(ends_m, h, G, lo, n);
-    e1 = msp_end(ends_m, g, G, lo, n);
-    if (g < G - 1) {
-      float* rrow = Rrow + g * level;
-#pragma unroll
-      for (int i = 0; i < DLW; ++i) {
-        const int col = col0 + i * WSP_T;
-        if (col < d) {
-          acc[i] += rrow[col];
-          rrow[col] = acc[i];
-        }
-      }
-    }
+    const int lo = msp_level_span(ends_m, g, G, n, e1);
+    if (g < G - 1) msp_level_down<DLW, WSP_T>(acc, Rrow + g * level, d, col0);
     if (one_fill) {
       wsp_gpre<DLW>(acc, L, g ? L.level_hi[g - 1] : 0, L.level_hi[g], W, inv, grow, gscale, d, col0,
                     lane, wave);
@@ -340,46 +313,18 @@ void k_sparse_hit_lists(const float* __restrict__ c,   // [M, B, n]
                         int* __restrict__ hit_counts,  // [M, n]
                         int B, int n) {
   __shared__ int cnt[SGW_NW][SGW_STRIP];
-  const int lane = spk_tid() & (WAVE - 1);
-  const int wave = spk_wave_id();
   const int m = (int)__builtin_amdgcn_workgroup_id_y();
-  const int j = (int)__builtin_amdgcn_workgroup_id_x() * SGW_STRIP + lane;
-  const bool j_ok = j < n;
-  // thread (slice = wave, feature = lane)
-  const int per = (B + SGW_NW - 1) / SGW_NW;
-  const int b_lo = spk_min(B, wave * per), b_hi = spk_min(B, b_lo + per);
-  const float* ccol = c + (long)m * B * n + (j_ok ? j : 0);
-  int k = 0;
-  if (j_ok) {
-#pragma unroll 8
-    for (int b = b_lo; b < b_hi; ++b) k += ccol[(long)b * n] > 0.f ? 1 : 0;
-  }
-  cnt[wave][lane] = k;
-  spk_barrier();
-  int off = 0, total = 0;
-#pragma unroll
-  for (int s = 0; s < SGW_NW; ++s) {
-    const int v = cnt[s][lane];
-    if (s < wave) off += v;
-    total += v;
-  }
-  if (j_ok) {
-    int* list = hits + ((long)m * n + j) * B;
-#pragma unroll 8
-    for (int b = b_lo; b < b_hi; ++b)
-      if (ccol[(long)b * n] > 0.f) list[off++] = b;
-    if (wave == 0) hit_counts[(long)m * n + j] = total;
-  }
+  sgw_hit_lists((int)__builtin_amdgcn_workgroup_id_x() * SGW_STRIP, c + (long)m * B * n,
+                hits + (long)m * n * B, hit_counts + (long)m * n, B, n, spk_lds(cnt),
+                spk_tid() & (WAVE - 1), spk_wave_id());
 }
 
 // ---------------------------------------------------------------------------
 // k_wsparse_grad_w: k_sparse_grad_w's phase 2 on one window of WSGW_CHUNK
 // columns.  grid (ceil(n / 64), ceil(d / 1024), M); block SGW_T.  The phase is
-// independent per column, so a window is the narrow kernel at DL = 16 with its
-// row pointers moved to the window's first column: the same light (<= 32 hits,
-// one wave) and heavy (8 slices, LDS combine in ascending slice order) rule,
-// the same sgw_accum.  A feature's residual rows come from its level of R
-// (r itself at G = 1).  Every row of gw is stored, +0 without a hit.
+// independent per column, so a window is sgw_strip_sums at DL = 16 with its row
+// pointers moved to the window's first column and the window's width for d:
+// the light/heavy rule and the order of every sum are the narrow kernel's.
 // The launch bounds ask for 2 waves per SIMD, not the 4 that 128 registers
 // allow: asked for 4, the compiler keeps 128 and spills 12 bytes; asked for 2,
 // it takes the same 128 and spills nothing.
@@ -394,7 +339,6 @@ void k_wsparse_grad_w(const float* __restrict__ c,             // [M, B, n]
                       const int* __restrict__ hits,            // [M, n, B], from k_sparse_hit_lists
                       const int* __restrict__ hit_counts,      // [M, n]
                       int B, int d, int n, int G, long x_mstride) {
-  constexpr int DL = WSGW_DL;
   __shared__ int tot[SGW_STRIP];
   __shared__ float part[SGW_NW][WSGW_CHUNK];
 
@@ -403,52 +347,13 @@ void k_wsparse_grad_w(const float* __restrict__ c,             // [M, B, n]
   const int m = (int)__builtin_amdgcn_workgroup_id_z();
   const int j0 = (int)__builtin_amdgcn_workgroup_id_x() * SGW_STRIP;
   const int c0 = (int)__builtin_amdgcn_workgroup_id_y() * WSGW_CHUNK;  // the window's first column
-  const int dw = spk_min(WSGW_CHUNK, d - c0);                          // and its width
   const long level = (long)B * d;
-  const float* c_m = c + (long)m * B * n;
-  const float* g_m = gpre + (long)m * B * n;
-  const float* R_m = R + (long)m * G * level + c0;
-  const int* ends_m = ends + (long)m * G;
-  const float* x_m = x + (long)m * x_mstride + c0;
-  float* gw_m = gw + (long)m * n * d + c0;
-  const float gscale = 2.0f / ((float)B * (float)d);
 
   if (wave == 0) tot[lane] = j0 + lane < n ? hit_counts[(long)m * n + j0 + lane] : 0;
   spk_barrier();
 
-  // ---- light features, one wave each ----------------------------------------
-  float acc[DL];
-  for (int f = wave; f < SGW_STRIP && j0 + f < n; f += SGW_NW) {
-    const int j = j0 + f;
-    const int count = tot[f];
-    if (count > SGW_LIGHT) continue;
-    sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, 0, count, c_m + j, g_m + j,
-                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, d, dw, lane);
-#pragma unroll
-    for (int i = 0; i < DL; ++i) {
-      const int col = lane + i * WAVE;
-      if (col < dw) gw_m[(long)j * d + col] = acc[i];
-    }
-  }
-
-  // ---- heavy features, all waves each ---------------------------------------
-  for (int f = 0; f < SGW_STRIP && j0 + f < n; ++f) {
-    const int count = tot[f];
-    if (count <= SGW_LIGHT) continue;  // block-uniform
-    const int j = j0 + f;
-    const int per = (count + SGW_NW - 1) / SGW_NW;
-    const int lo = spk_min(count, wave * per), hi = spk_min(count, lo + per);
-    sgw_accum<DL>(acc, hits + ((long)m * n + j) * B, lo, hi, c_m + j, g_m + j,
-                  msp_level_rows(R_m, ends_m, j, G, n, level), x_m, gscale, n, d, dw, lane);
-#pragma unroll
-    for (int i = 0; i < DL; ++i) part[wave][i * WAVE + lane] = acc[i];
-    spk_barrier();
-    for (int col = spk_tid(); col < dw; col += SGW_T) {
-      float s = part[0][col];
-#pragma unroll
-      for (int w = 1; w < SGW_NW; ++w) s += part[w][col];
-      gw_m[(long)j * d + col] = s;
-    }
-    spk_barrier();
-  }
+  sgw_strip_sums<WSGW_DL>(spk_lds(tot), spk_lds(part), j0, hits + (long)m * n * B, c + (long)m * B * n,
+                          gpre + (long)m * B * n, R + (long)m * G * level + c0, ends + (long)m * G,
+                          x + (long)m * x_mstride + c0, gw + (long)m * n * d + c0, B, n, G, level,
+                          2.0f / ((float)B * (float)d), d, spk_min(WSGW_CHUNK, d - c0), lane, wave);
 }

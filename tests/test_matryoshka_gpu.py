@@ -1,4 +1,4 @@
-"""The Matryoshka BatchTopK step: k_msparse_dec_gc + k_msparse_grad_w.
+"""The Matryoshka BatchTopK step: k_sparse_dec_gc + k_sparse_grad_w with LEVELS.
 
 1. HipMatryoshkaStep against fp64 autograd of the signature's own loss, under
    8 e32 + 16 U scale.  Its only nonsmooth decision is BatchTopK's selection
@@ -92,7 +92,7 @@ CASES = [((2, 70, 68, 132), ((64, 128, 132), (37, 101, 132))), ((1, 6, 2048, 70)
          ((1, 40, 2044, 66), ((3, 8, 13, 21, 30, 41, 64, 66),)), ((2, 70, 68, 132), ((132,), (132,)))]
 # The depths between (DL = 4, 8, 12, 16) and DL = 32 entered from below, ends off
 # multiples of 4 and 64; B >= 34 makes column 1 a heavy feature.  d = 1024 is
-# k_msparse_dec_gc's 4-waves-per-SIMD instantiation, at G = 8 with the most
+# k_sparse_dec_gc<16, 4, LEVELS>, the 4-waves-per-SIMD instantiation, at G = 8 with the most
 # levels live around its 16 registers; G = 1 at d = 768 meets the plain kernels
 # bit for bit where the LDS combine is 768 wide.
 CASES += [((2, 38, 256, 132), ((64, 128, 132), (37, 101, 132))), ((1, 40, 260, 70), ((33, 70),)),

@@ -1,7 +1,7 @@
 """The shapes of the sparse and Matryoshka kernel tests against the register
 depths the launchers compile.
 
-k_sparse_dec_gc, k_sparse_grad_w and their Matryoshka twins are templates over
+k_sparse_dec_gc and k_sparse_grad_w, plain and with levels, are templates over
 DL; SPARSE_DISPATCH_DL (sae_ops.hip) lists the compiled depths and takes the
 smallest one >= ceil(d / 64).  The GPU tests are written against that list:
 every depth has to run full or nearly so, and every depth above 2 also at a d
