@@ -76,6 +76,12 @@ def build(sig_name, d, n, M, device):
         ends = [n // 16, n // 8, n // 4, n // 2, n]
         models = [sig.init(d, n, 32, ends) for _ in range(M)]
         no_stacking = True  # as batch_topk
+    elif sig_name == "jumprelu":
+        from sparse_coding_amd.models.jumprelu import JumpReLUEncoder
+
+        sig = JumpReLUEncoder
+        # x.What is N(0, 1) at the initial dictionary: 2.418 keeps 32 of 4096 per row
+        models = [sig.init(d, n, float(l1), threshold=2.418) for l1 in l1s]
     elif sig_name == "lista":
         sig = FunctionalLISTADenoisingSAE
         models = [sig.init(d, n, 3, float(l1)) for l1 in l1s]
@@ -130,7 +136,8 @@ def main():
     device = "cuda:0"
 
     sig_names = ("tied", "untied", "masked_tied", "thresholding", "reverse",
-                 "centered", "whitened", "positive", "topk", "batch_topk", "matryoshka", "lista",
+                 "centered", "whitened", "positive", "topk", "batch_topk", "matryoshka", "jumprelu",
+                 "lista",
                  "residual", "semilinear")
     if args.only:
         sig_names = tuple(s for s in sig_names if s in args.only.split(","))

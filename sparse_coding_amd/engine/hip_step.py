@@ -30,7 +30,8 @@ hand-written gfx950 HIP kernels (``sparse_coding_amd/ops/hip/sae_kernels.hip``):
 
 Fused-step coverage: EVERY trainable signature in the zoo — tied, untied,
 masked tied/untied, thresholding, reverse, tied-centered, positive-tied,
-TopK, BatchTopK, Matryoshka BatchTopK, LISTA, residual-denoising and semilinear.
+TopK, BatchTopK, Matryoshka BatchTopK, LISTA, residual-denoising and semilinear;
+TopK with AuxK and JumpReLU live in engine/hip_auxk.py and engine/hip_jumprelu.py.
 
 Structure.  Every step class derives from ``_HipStep``, which owns what
 does not depend on the signature: the Adam hyper-parameters, the kernel
@@ -117,6 +118,8 @@ def maybe_make_step(ensemble, required: bool = False) -> Optional["_HipStep"]:
     from sparse_coding_amd.models.topk import TopKEncoder
     from sparse_coding_amd.engine.hip_auxk import HipTopKAuxStep
     from sparse_coding_amd.models.topk_auxk import TopKAuxEncoder
+    from sparse_coding_amd.engine.hip_jumprelu import HipJumpReLUStep
+    from sparse_coding_amd.models.jumprelu import JumpReLUEncoder
 
     def sae(**flags):
         return lambda ens, ext: HipSAEStep(ens, ext, **flags)
@@ -126,6 +129,7 @@ def maybe_make_step(ensemble, required: bool = False) -> Optional["_HipStep"]:
         TopKAuxEncoder: HipTopKAuxStep,
         BatchTopKEncoder: HipBatchTopKStep,
         MatryoshkaBatchTopKEncoder: HipMatryoshkaStep,
+        JumpReLUEncoder: HipJumpReLUStep,
         sigs.FunctionalThresholdingSAE: HipThresholdStep,
         sigs.FunctionalReverseSAE: sae(tied=True, reverse=True),
         sigs.FunctionalTiedCenteredSAE: HipCenteredStep,

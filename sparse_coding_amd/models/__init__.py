@@ -9,6 +9,7 @@ from sparse_coding_amd.models.sae_signatures import (
 )
 from sparse_coding_amd.models.topk import TopKEncoder, TopKLearnedDict
 from sparse_coding_amd.models.topk_auxk import TopKAuxEncoder
+from sparse_coding_amd.models.jumprelu import JumpReLUEncoder, JumpReLULearnedDict
 from sparse_coding_amd.models.batch_topk import BatchTopKEncoder, BatchTopKLearnedDict
 from sparse_coding_amd.models.matryoshka import (
     MatryoshkaBatchTopKEncoder, MatryoshkaBatchTopKLearnedDict,

@@ -8,6 +8,7 @@
 #include "sae_kernels.hip"
 #include "sae_wsparse.hip"
 #include "sae_auxk.hip"
+#include "sae_jumprelu.hip"
 
 static inline void check_in(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
@@ -750,6 +751,69 @@ void auxk_grad_w(torch::Tensor aux_idx, torch::Tensor aux_val, torch::Tensor aux
 #undef LAUNCH_AXGW
 }
 
+// The JumpReLU step's kernels (sae_jumprelu.hip).  Per model: threshold [n],
+// bandwidth and l0_alpha fp32 scalars.  band_bits is int64 [M, B, ceil(n / 64)]:
+// bit l of word g of a row is the band of column 64 g + l.
+struct JumpShape {
+  int M, B, n, NW;
+  unsigned long long* bits;
+};
+
+static JumpShape jump_shape(const char* who, const torch::Tensor& band_bits, const torch::Tensor& threshold,
+                            const torch::Tensor& bandwidth) {
+  check_in(threshold, "threshold");
+  check_in(bandwidth, "bandwidth");
+  TORCH_CHECK(band_bits.is_cuda() && band_bits.is_contiguous() && band_bits.scalar_type() == torch::kInt64 &&
+              band_bits.dim() == 3, who, ": band_bits must be int64 GPU [M,B,ceil(n/64)]");
+  TORCH_CHECK(threshold.dim() == 2 && threshold.size(0) == band_bits.size(0), who,
+              ": threshold must be [M,n]");
+  const long M = band_bits.size(0), B = band_bits.size(1), n = threshold.size(1);
+  TORCH_CHECK(n >= 1 && n < (1L << 31) && B < (1L << 31) && M <= 65535, who, ": M, B or n out of range");
+  TORCH_CHECK(band_bits.size(2) == (n + WAVE - 1) / WAVE, who, ": band_bits must hold ceil(n/64) words per row");
+  TORCH_CHECK(bandwidth.numel() == M, who, ": bandwidth must be [M]");
+  return {(int)M, (int)B, (int)n, (int)band_bits.size(2),
+          reinterpret_cast<unsigned long long*>(band_bits.data_ptr<int64_t>())};
+}
+
+void jump_select(torch::Tensor scores, torch::Tensor threshold, torch::Tensor bandwidth, torch::Tensor c_out,
+                 torch::Tensor fired, torch::Tensor band_bits, torch::Tensor l0_count) {
+  CHECK_IN(scores); CHECK_IN(c_out); CHECK_IN(fired);
+  const JumpShape s = jump_shape("jump_select", band_bits, threshold, bandwidth);
+  TORCH_CHECK(scores.dim() == 3 && scores.size(0) == s.M && scores.size(1) == s.B && scores.size(2) == s.n,
+              "jump_select: scores must be [M,B,n]");
+  TORCH_CHECK(c_out.sizes() == scores.sizes(), "jump_select: c_out must have the shape of scores");
+  TORCH_CHECK(fired.numel() == (long)s.M * s.n, "jump_select: fired must be [M,n]");
+  TORCH_CHECK(l0_count.numel() == s.M, "jump_select: l0_count must be [M]");
+  int* l0_p = int32_ptr(l0_count, "l0_count");
+  if (s.M == 0 || s.B == 0) return;
+  hipLaunchKernelGGL(k_jump_select, dim3(cdiv(s.B, JSL_ROWS), s.M), dim3(JSL_T), 0, cur_stream(),
+                     scores.data_ptr<float>(), threshold.data_ptr<float>(), bandwidth.data_ptr<float>(),
+                     c_out.data_ptr<float>(), fired.data_ptr<float>(), s.bits, l0_p, s.B, s.n, s.NW);
+}
+
+void jump_grad_theta(torch::Tensor band_bits, torch::Tensor W, torch::Tensor inv_norms, torch::Tensor r,
+                     torch::Tensor threshold, torch::Tensor bandwidth, torch::Tensor l0_alpha,
+                     torch::Tensor g_theta) {
+  CHECK_IN(W); CHECK_IN(inv_norms); CHECK_IN(r); CHECK_IN(l0_alpha); CHECK_IN(g_theta);
+  const JumpShape s = jump_shape("jump_grad_theta", band_bits, threshold, bandwidth);
+  TORCH_CHECK(W.dim() == 3 && W.size(0) == s.M && W.size(1) == s.n, "jump_grad_theta: W must be [M,n,d]");
+  const long d = W.size(2);
+  TORCH_CHECK(d >= 1 && d < (1L << 31), "jump_grad_theta: d out of range");
+  TORCH_CHECK(r.dim() == 3 && r.size(0) == s.M && r.size(1) == s.B && r.size(2) == d,
+              "jump_grad_theta: r must be [M,B,d]");
+  TORCH_CHECK(inv_norms.numel() == (long)s.M * s.n && g_theta.numel() == (long)s.M * s.n,
+              "jump_grad_theta: inv_norms and g_theta must be [M,n]");
+  TORCH_CHECK(l0_alpha.numel() == s.M, "jump_grad_theta: l0_alpha must be [M]");
+  if (s.M == 0) return;
+  // float4 loads: every row of W and r starts on a 16-byte boundary
+  const auto at16 = [](const torch::Tensor& t) { return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0; };
+  const int vec = d % 4 == 0 && at16(W) && at16(r);
+  hipLaunchKernelGGL(k_jump_grad_theta, dim3(s.NW, s.M), dim3(JGT_T), 0, cur_stream(),
+                     (const unsigned long long*)s.bits, W.data_ptr<float>(), inv_norms.data_ptr<float>(),
+                     r.data_ptr<float>(), threshold.data_ptr<float>(), bandwidth.data_ptr<float>(),
+                     l0_alpha.data_ptr<float>(), g_theta.data_ptr<float>(), s.B, (int)d, s.n, s.NW, vec);
+}
+
 void resample(torch::Tensor fired, torch::Tensor new_rows, torch::Tensor enc_scale,
               torch::Tensor W, torch::Tensor mu_w, torch::Tensor nu_w,
               c10::optional<torch::Tensor> dec,
@@ -874,6 +938,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("aux_idx"), py::arg("aux_val"), py::arg("aux_cnt"), py::arg("gpre_aux"), py::arg("r_aux"),
         py::arg("x"), py::arg("ages"), py::arg("dead_after"), py::arg("k_aux"), py::arg("n_dead"),
         py::arg("alpha"), py::arg("gw"));
+  m.def("jump_select", &jump_select,
+        "c = scores where scores > max(threshold, 0), else +0 (+ fired, l0_count), and the band "
+        "|scores - threshold| < bandwidth / 2 as one ballot word per 64 columns of a row",
+        py::arg("scores"), py::arg("threshold"), py::arg("bandwidth"), py::arg("c_out"), py::arg("fired"),
+        py::arg("band_bits"), py::arg("l0_count"));
+  m.def("jump_grad_theta", &jump_grad_theta,
+        "g_theta[j] = -(1/eps) sum over the band's rows of theta[j] g_f[b,j] + l0_alpha / B; no atomics",
+        py::arg("band_bits"), py::arg("W"), py::arg("inv_norms"), py::arg("r"), py::arg("threshold"),
+        py::arg("bandwidth"), py::arg("l0_alpha"), py::arg("g_theta"));
   m.def("resample", &resample, "fused dead-neuron resample (K14): rank dead, rewrite rows, zero Adam state",
         py::arg("fired"), py::arg("new_rows"), py::arg("enc_scale"),
         py::arg("W"), py::arg("mu_w"), py::arg("nu_w"),

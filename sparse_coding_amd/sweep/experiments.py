@@ -23,6 +23,7 @@ import torch
 from sparse_coding_amd.engine.ensemble import FunctionalEnsemble
 from sparse_coding_amd.functional.optim import adam
 from sparse_coding_amd.models.batch_topk import BatchTopKEncoder
+from sparse_coding_amd.models.jumprelu import JumpReLUEncoder
 from sparse_coding_amd.models.matryoshka import MatryoshkaBatchTopKEncoder
 from sparse_coding_amd.models.sae_signatures import (
     FunctionalMaskedTiedSAE,
@@ -184,6 +185,22 @@ def matryoshka_init(cfg, ks: Sequence[int] = (4, 8, 16, 32, 64, 128), n_levels: 
     )
 
 
+def jumprelu_init(cfg, l0_alphas: Sequence[float] = tuple(np.logspace(-5, -2, 8))):
+    """JumpReLU SAEs across L0 penalties, with a learned per-feature threshold."""
+    d = cfg.activation_width
+    devices = default_devices()
+    n_dict = int(d * cfg.learned_dict_ratio)
+    models = [JumpReLUEncoder.init(d, n_dict, float(a)) for a in l0_alphas]
+    ens = FunctionalEnsemble(models, JumpReLUEncoder, adam, {"lr": cfg.lr}, device=devices[0])
+    args = {"batch_size": cfg.batch_size, "device": devices[0], "dict_size": n_dict}
+    return (
+        [(ens, args, "jumprelu")],
+        ["dict_size"],
+        ["l0_alpha"],
+        {"l0_alpha": [float(a) for a in l0_alphas], "dict_size": [n_dict]},
+    )
+
+
 def thresholding_init(cfg):
     """Soft-thresholding SAEs (reference :403-494)."""
     return make_grid_ensembles(cfg, FunctionalThresholdingSAE, np.logspace(-4, -2, 8))
@@ -211,6 +228,10 @@ def run_batch_topk(cfg):
 
 def run_matryoshka(cfg):
     return sweep(matryoshka_init, cfg)
+
+
+def run_jumprelu(cfg):
+    return sweep(jumprelu_init, cfg)
 
 
 def run_across_layers(cfg, layers: Sequence[int], init: Callable = dense_l1_range_init):
